@@ -8,7 +8,15 @@ ModifiedResNet((3,4,6,3), output_dim=512) at 224x224 in bf16 (BASELINE.json
 configs[1]; configs[2] at --gpus 8).  Data-parallel over RCCL when launched
 with torch.distributed.run.  Prints ONE JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline]
+A plain run sets up, warms up, times the K steps and prints the line.  --full
+adds everything else the line can carry: the f32 step-0 loss check, the
+per-launch roofline pass, the embed / C5 / preprocess / retrieval legs and the
+CPU baselines (each with its own --no-... switch).  --dump-outputs DIR writes
+what the last timed step computed as DIR/timed/<name>.npy, then runs the step
+once more, made repeatable, and writes that as DIR/<name>.npy (dump_outputs).
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] ...]
 """
 from __future__ import annotations
 
@@ -35,7 +43,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md; ~6.3 TB/s measu
 # (training step + retrieval scan, eval-BN embed pass, C5 ViT step), so a leg's
 # roofline only takes traffic measured on that leg's own launches.
 # the autotuner's choices for every shape of every leg on MI355X (a find-db:
-# `bench.py --tune-cache none --tune-save FILE` regenerates it); the PMC traffic
+# `bench.py --full --tune-cache none --tune-save FILE` regenerates it); the PMC traffic
 # files below were measured with it loaded, so a kernel name stands for the
 # same launches in both
 TUNE_CACHE = os.path.join(ROOT, "profiles", "tune_r6.txt")
@@ -567,6 +575,56 @@ def launch_check(world, rank):
     dist.destroy_process_group()
 
 
+DUMP_SAMPLE = 16384  # elements sampled of each parameter tensor
+
+
+def dump_outputs(path, loss, outs, model):
+    """--dump-outputs: what the caller of one step receives, as float32
+    DIR/<name>.npy — the loss, the three branch embeddings [B, 512], and the
+    step's effect on the model: every BatchNorm running statistic in full, and of
+    each parameter and of its gradient a sample of up to DUMP_SAMPLE elements
+    (indices drawn once from a generator seeded with 0: the same in every run),
+    concatenated in model.named_parameters() order.  About 11 MB in all.
+
+    main() writes two such sets.  DIR/timed/<name>.npy is the last timed step
+    itself, after W + K steps in the timed kernels.  Those arrays are NOT
+    repeatable: at its random init the train-mode network amplifies rounding
+    (tests/test_c2_gpu.py, "Conditioning"), and with the timed mode's atomic
+    BatchNorm sums ONE step from identical inputs and weights already differs
+    from run to run by 6 % in the embeddings and has uncorrelated gradients
+    (spread after W + K steps: DESIGN §5).  DIR/<name>.npy, the set to compare
+    two builds by, is the last call the run makes of the same step function,
+    after the timed region: from the seeded initial weights with a fresh Adam,
+    in the library's fixed-order reduction mode (engine.set_deterministic, which
+    takes the atomic forward statistics and the fused BN-backward epilogues out).
+    Its loss, embeddings and running statistics are bit-identical from run to
+    run and do not depend on --steps / --warmup; gradients differ by summation
+    order (rel. L2 3e-5) and 0.1 % of the parameters by 2 lr, where Adam's first
+    step takes the sign of a rounding-level gradient."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    g = torch.Generator().manual_seed(0)
+    params, grads = [], []
+    for _, p in model.named_parameters():
+        flat = p.detach().reshape(-1)
+        grad = (p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=g).to(flat.device)
+            flat, grad = flat[idx], grad[idx]
+        params.append(flat.float().cpu())
+        grads.append(grad.float().cpu())
+    stats = [b.detach().reshape(-1).float().cpu() for _, b in model.named_buffers() if b.is_floating_point()]
+    arrays = {"loss": loss.detach().float().reshape(1).cpu(),
+              "embedding_sketch": outs[0].detach().float().cpu(),
+              "embedding_positive": outs[1].detach().float().cpu(),
+              "embedding_negative": outs[2].detach().float().cpu(),
+              "params_sample": torch.cat(params), "grads_sample": torch.cat(grads)}
+    if stats:
+        arrays["bn_running_stats"] = torch.cat(stats)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.numpy().astype(np.float32, copy=False))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
@@ -574,9 +632,18 @@ def main():
                          "N > 1 starts the N ranks itself under torch.distributed.run")
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--warmup", type=int, default=2, help="untimed steps before the timed ones (at least 1 is run; "
+                                                          "the line's `warmup` is the number run)")
     ap.add_argument("--batch", type=int, default=384, help="triplets per GPU per step")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the timed steps: the f32 step-0 loss check, the per-launch "
+                         "roofline pass, the embed / C5 / preprocess / retrieval legs and the CPU baselines "
+                         "(the --no-... switches below each take one of them out again)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's results as DIR/timed/<name>.npy (float32; not repeatable from "
+                         "run to run), then run the step once more from the seeded initial state in the fixed-order "
+                         "reduction mode and write its results as DIR/<name>.npy (repeatable: the set to compare)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="skip the live per-launch event timing")
     ap.add_argument("--no-retrieval", action="store_true", help="skip the 1M x 512 kNN leg")
@@ -597,6 +664,13 @@ def main():
     ap.add_argument("--tune-save", default=None,
                     help="write the autotuner's choices after every leg has run (shapes of all legs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run: the timed steps alone
+        args.no_loss_check = args.no_profile = args.no_embed = args.no_preprocess = True
+        args.no_retrieval = args.no_cpu_baseline = True
+        args.c5 = False
 
     env_world = os.environ.get("WORLD_SIZE")
     if args.gpus is None:
@@ -668,6 +742,9 @@ def main():
         model.load_state_dict(saved, strict=False)
         torch.cuda.empty_cache()
 
+    # --dump-outputs replays one step from the state the first step starts from
+    initial = {k: v.clone() for k, v in model.state_dict().items()} if args.dump_outputs else None
+
     reducer = ddp.attach_overlapped_reducer(model)
 
     def step():
@@ -679,7 +756,7 @@ def main():
         loss.backward()  # N > 1: all-reduce buckets start inside the backward (ddp.OverlappedReducer)
         reducer.finish()
         opt.step()
-        return loss
+        return loss, outs
 
     # the step runs on a high-priority stream: the dispatcher then serves the
     # HBM-bound data-gradient / BatchNorm chain first and the weight gradients
@@ -688,8 +765,9 @@ def main():
     if prio:
         torch.cuda.set_stream(torch.cuda.Stream(device=dev, priority=prio))
     loss0 = None
-    for i in range(max(args.warmup, 1)):
-        li = step()
+    warmup = max(args.warmup, 1)  # at least one: the first step allocates, loads the code objects and gives loss_step0
+    for i in range(warmup):
+        li, _ = step()
         if i == 0:
             loss0 = float(li.item())
         if args.sync_warmup:
@@ -707,7 +785,7 @@ def main():
     t0 = time.perf_counter()
     step_ev[0].record()
     for i in range(args.steps):
-        loss = step()
+        loss, outs = step()
         step_ev[i + 1].record()
     torch.cuda.synchronize()
     if world > 1:
@@ -720,6 +798,29 @@ def main():
         elapsed = float(t.item())
     last_loss = float(loss.item())
     ms1 = torch.cuda.memory_stats(dev)
+    if args.dump_outputs:
+        if rank == 0:  # the last timed step itself
+            dump_outputs(os.path.join(args.dump_outputs, "timed"), loss, outs, model)
+        # one more call of the timed step, made repeatable (dump_outputs): from the
+        # seeded initial state, with a fresh Adam, in the fixed-order reduction mode;
+        # the model and the optimizer then go back to where the timed steps left them
+        import engine
+        after = {k: v.clone() for k, v in model.state_dict().items()}
+        timed_opt, opt = opt, optim.Adam(model.parameters(), lr=1e-5, weight_decay=0.002)
+        model.load_state_dict(initial)
+        engine.bump_weights_generation()
+        was = engine.set_deterministic(True)
+        try:
+            dloss, douts = step()
+            torch.cuda.synchronize()
+            if rank == 0:
+                dump_outputs(args.dump_outputs, dloss, douts, model)
+            del dloss, douts
+        finally:
+            engine.set_deterministic(was)
+            opt = timed_opt
+            model.load_state_dict(after)
+            engine.bump_weights_generation()
     alloc = {"step_ms": [round(step_ev[i].elapsed_time(step_ev[i + 1]), 2) for i in range(args.steps)],
              "retries_timed": ms1.get("num_alloc_retries", 0) - ms0.get("num_alloc_retries", 0),
              "device_mallocs_timed": ms1.get("num_device_alloc", 0) - ms0.get("num_device_alloc", 0),
@@ -744,7 +845,7 @@ def main():
             "metric": "triplet-images/sec embedded @224² bf16, 1→8 GPU; gallery kNN QPS @1M×512",
             "value": round(value, 2), "unit": "triplet-images/s", "n_gpus": world, "world_size": world,
             "backend": backend, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
+            "warmup": warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
             "config": {"workload": "triplet training step (train.py:59-70): 3x encoder fwd + TripletMarginLoss "
                                    "+ backward + Adam", "model": "ModifiedResNet((3,4,6,3), output_dim=512)",

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Per-kernel HBM traffic from two rocprofv3 PMC passes of bench.py.
 
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -o run -- python3 bench.py ...
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -o run -- python3 bench.py ...
-    python profiles/summarize_pmc.py gpurun_out/pmc_train gpurun_out/pmc_retr profiles/r2_pmc_traffic.json
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d OUT/pmc_fetch -o run -- python3 bench.py --full ...
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d OUT/pmc_write -o run -- python3 bench.py --full ...
+    python profiles/summarize_pmc.py OUT/pmc_train OUT/pmc_retr profiles/r2_pmc_traffic.json
 
 Counter values are KiB.  gfx950 correction (MI355X_MICROARCH.md §HBM):
 FETCH_SIZE reports half the bytes of a wide coalesced stream -> doubled (exact
