@@ -188,6 +188,9 @@ SIGNATURES = {
                                  _vp, _vp, _vp, _vp, _vp, _c_ll, _vp],
     "artsbir_scan_profile": [_c_int],
     "artsbir_knn_set_unc_cap": [_c_int],
+    "artsbir_knn_set_cand_cap": [_c_int],
+    "artsbir_knn_largek_stat_read": [ctypes.POINTER(ctypes.c_longlong), _c_int],
+    "artsbir_knn_exact_keys": [_c_int, _vp, _c_int, _vp, _c_ll, _c_int, _vp, _vp],
     "artsbir_scan_profile_read": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_int)],
     "artsbir_knn_stat_read": [ctypes.POINTER(ctypes.c_ulonglong), _c_int],
     "artsbir_topk_merge": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp],

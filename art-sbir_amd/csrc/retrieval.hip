@@ -240,11 +240,17 @@ struct KnnScanArgs {
   int unc_cap;
   float* cand_d;    // [Nq][nchunks][KT]
   int* cand_i;
+  // collect mode (template parameter CM of the scans, the large-k path): every row
+  // with approximate d2 under the query's thr0 is appended to col_i[q][col_cap]
+  // through the counter col_n[q] (which keeps counting past col_cap)
+  int* col_n;
+  int* col_i;
+  int col_cap;
 };
 
 constexpr int KT = 16;  // per (query, chunk) candidate list length
 
-template <typename T>
+template <typename T, int CM = 0>
 __global__ void __launch_bounds__(256) knn_scan_kernel(KnnScanArgs a) {
   constexpr int EPC = RM<T>::EPC;
   constexpr int ES = sizeof(T);
@@ -304,6 +310,7 @@ __global__ void __launch_bounds__(256) knn_scan_kernel(KnnScanArgs a) {
   const float lo = (a.lo && row_ok) ? a.lo[bm + my_row] : -1.f;
   const float hi = (a.lo && row_ok) ? a.hi[bm + my_row] : -1.f;
   const float qsq = row_ok ? a.qsq[bm + my_row] : 0.f;
+  const float cthr = (CM && row_ok) ? a.thr0[bm + my_row] : -INFINITY;  // collect mode: the query's cut
   if (tid < BM) s_thr[tid] = INFINITY;
 
   uint4 ra[4], rb[4];
@@ -379,7 +386,12 @@ __global__ void __launch_bounds__(256) knn_scan_kernel(KnnScanArgs a) {
         for (int e = 0; e < 4; ++e) {
           const int c = my_half * 64 + c4 + e;
           const float d2 = qsq + s_gsq[c] - 2.f * sv[e];
-          if (d2 < thr && thr != INFINITY) {
+          if constexpr (CM) {
+            if (d2 <= cthr && bn + c < a.Ng) {
+              const int slot = atomicAdd(a.col_n + bm + my_row, 1);
+              if (slot < a.col_cap) a.col_i[(long long)(bm + my_row) * a.col_cap + slot] = bn + c;
+            }
+          } else if (d2 < thr && thr != INFINITY) {
             const int slot = atomicAdd(&s_qn[my_row], 1);
             if (slot < 8) { s_qd[my_row][slot] = d2; s_qi[my_row][slot] = bn + c; }
           }
@@ -398,7 +410,7 @@ __global__ void __launch_bounds__(256) knn_scan_kernel(KnnScanArgs a) {
     // the owner merges the queued values into its sorted register list; if the
     // list was not yet full (first tile) or the queue overflowed, it rescans the
     // whole staged row instead
-    if (owner && row_ok) {
+    if (!CM && owner && row_ok) {
       const int nq = s_qn[my_row];
       auto insert = [&](float x, int xi) {
 #pragma unroll
@@ -428,7 +440,7 @@ __global__ void __launch_bounds__(256) knn_scan_kernel(KnnScanArgs a) {
   }
   if (row_ok) {
     if (closer) atomicAdd(a.cnt + bm + my_row, closer);
-    if (owner) {
+    if (!CM && owner) {
       const long long o = ((long long)(bm + my_row) * a.nchunks + chunk) * KT;
 #pragma unroll
       for (int i = 0; i < KT; ++i) {
@@ -604,7 +616,10 @@ static bool knn_stat_on() {
 // 2 KB registers per lane at D = 512, AGPRs included), so each B fragment read
 // from LDS feeds two MFMAs — half the LDS reads per MAC — and every lane owns a
 // query row in the list / slow path (ARTSBIR_KNN_QH, knn_qh())
-template <int KB, int QH = 1>
+// CM 1 (collect mode, the large-k path): thr0 is the query's fixed cut; a row under
+// it is appended to the query's candidate buffer instead of entering the list, and
+// no list is written
+template <int KB, int QH = 1, int CM = 0>
 __global__ void __launch_bounds__(64 * V2_WAVES / QH, 1) knn_scan_v2_kernel(KnnScanArgs a, int stat) {
   using C = V2<KB>;
   constexpr int NWV = V2_WAVES / QH;  // waves of the workgroup
@@ -855,7 +870,13 @@ __global__ void __launch_bounds__(64 * V2_WAVES / QH, 1) knn_scan_v2_kernel(KnnS
           const bool valid = bn + c < a.Ng;
           const float g2 = sg[c * gstr];
           const float d2 = fmaf(-2.f, srow[c], qs + g2);
-          if (d2 < thr) {
+          if (CM) {
+            if (d2 < thr && valid && q_own < a.Nq) {
+              const int slot = atomicAdd(a.col_n + q_own, 1);
+              if (slot < a.col_cap) a.col_i[(long long)q_own * a.col_cap + slot] = bn + c;
+              atom = true;
+            }
+          } else if (d2 < thr) {
             ++st_ins;
             float x = d2;
             int xi = bn + c;
@@ -987,11 +1008,13 @@ __global__ void __launch_bounds__(64 * V2_WAVES / QH, 1) knn_scan_v2_kernel(KnnS
     const int q = qb + R_own;
     if (q < a.Nq) {
       if (mycnt) atomicAdd(a.cnt + q, mycnt);
-      const long long o = ((long long)q * a.nchunks + chunk) * KT;
+      if (!CM) {
+        const long long o = ((long long)q * a.nchunks + chunk) * KT;
 #pragma unroll
-      for (int i = 0; i < KT; ++i) {
-        a.cand_d[o + i] = lst_d[i];
-        a.cand_i[o + i] = lst_i[i];
+        for (int i = 0; i < KT; ++i) {
+          a.cand_d[o + i] = lst_d[i];
+          a.cand_i[o + i] = lst_i[i];
+        }
       }
     }
   }
@@ -1014,6 +1037,16 @@ static void knn_scan_v2_launch(int Dp, unsigned grid, const KnnScanArgs& a, int 
     case 128: hipLaunchKernelGGL((knn_scan_v2_kernel<8, 1>), g, dim3(512), 0, st, a, stat); break;
     case 256: hipLaunchKernelGGL((knn_scan_v2_kernel<16, 1>), g, dim3(512), 0, st, a, stat); break;
     default: hipLaunchKernelGGL((knn_scan_v2_kernel<32, 1>), g, dim3(512), 0, st, a, stat); break;
+  }
+}
+
+static void knn_scan_v2_collect_launch(int Dp, unsigned grid, const KnnScanArgs& a, hipStream_t st) {
+  const dim3 g(grid);
+  switch (Dp) {
+    case 64: hipLaunchKernelGGL((knn_scan_v2_kernel<4, 1, 1>), g, dim3(512), 0, st, a, 0); break;
+    case 128: hipLaunchKernelGGL((knn_scan_v2_kernel<8, 1, 1>), g, dim3(512), 0, st, a, 0); break;
+    case 256: hipLaunchKernelGGL((knn_scan_v2_kernel<16, 1, 1>), g, dim3(512), 0, st, a, 0); break;
+    default: hipLaunchKernelGGL((knn_scan_v2_kernel<32, 1, 1>), g, dim3(512), 0, st, a, 0); break;
   }
 }
 
@@ -1630,6 +1663,203 @@ __global__ void __launch_bounds__(256) topk_lists_merge_kernel(const double* __r
   }
 }
 
+// ------------------------------------------------- large k (65 .. 1024)
+// The wave-resident merge and fallback above stop at k = 64.  For larger k the
+// one-call path keeps the scan and its chunk lists only to find a per-query cut:
+//   knn_lk_thresh_kernel   T = k-th smallest approximate d2 of the union of the
+//                          chunk lists (>= the gallery's k-th smallest a_k), cut =
+//                          T + 2 eps_q: by the argument of knn_merge_kernel step
+//                          (1) every true top-k row has approximate d2 <= cut;
+//   the scans' collect mode (CM) appends every row under the cut to a per-query
+//                          buffer of cand_cap indices;
+//   knn_lk_select_kernel   exact keys of the collected rows, sorted by (key,
+//                          index) in LDS, the first k written; a query whose
+//                          buffer overflowed or holds fewer than min(k, N) rows
+//                          is flagged instead;
+//   knn_lk_exhaustive_kernel  the flagged queries, by an exact scan of the gallery.
+// A gallery of at most cand_cap rows skips the cut: every row is a candidate.
+constexpr int LK_SORT = 4096;  // entries knn_lk_select_kernel sorts (48 KB of LDS): the largest cand_cap
+constexpr int LK_PAD = 0x7fffffff;
+__device__ unsigned long long g_knn_lk_stat[2];  // queries answered by the select path / the exhaustive fallback
+
+// the cut of one query (one wave): bisection over the order-preserving u32 keys
+// of the listed values, as knn_merge_wave_kernel step (1); -INF (nothing
+// collected, so the query is flagged) when the lists hold fewer than k rows.
+// The cut is rounded up and one ulp beyond (the v2 scan compares d2 < cut), with
+// 2^-20 relative room for a last-bit difference between the two passes' d2
+__global__ void __launch_bounds__(64) knn_lk_thresh_kernel(const float* __restrict__ cand_d,
+                                                           const int* __restrict__ cand_i, int nc, int k,
+                                                           const float* __restrict__ qeps, float* __restrict__ cthr) {
+  extern __shared__ char sm[];
+  unsigned* keys = reinterpret_cast<unsigned*>(sm);  // [nc]
+  const int qi = blockIdx.x, lane = threadIdx.x;
+  const float* cd = cand_d + (long long)qi * nc;
+  const int* ci = cand_i + (long long)qi * nc;
+  unsigned nvalid = 0;
+  for (int c = lane; c < nc; c += 64) {
+    const bool ok = ci[c] >= 0;
+    keys[c] = ok ? kb_enc(cd[c]) : 0xffffffffu;
+    nvalid += ok ? 1u : 0u;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) nvalid += __shfl_xor(nvalid, o, 64);
+  __syncthreads();
+  if (nvalid < (unsigned)k) {
+    if (lane == 0) cthr[qi] = -INFINITY;
+    return;
+  }
+  unsigned lo = 0u, hi = 0xfffffffeu;
+  while (lo < hi) {
+    const unsigned mid = lo + ((hi - lo) >> 1);
+    unsigned cnt = 0;
+    for (int c = lane; c < nc; c += 64) cnt += keys[c] <= mid ? 1u : 0u;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if (cnt >= (unsigned)k) hi = mid; else lo = mid + 1;
+  }
+  if (lane == 0) {
+    const double v = ((double)kb_dec(lo) + 2.0 * (double)qeps[qi]) * (1.0 + 0x1p-20);
+    float f = (float)v;
+    if ((double)f < v) f = nextafterf(f, INFINITY);
+    cthr[qi] = nextafterf(f, INFINITY);
+  }
+}
+
+// ascending bitonic sort of P = 2^m (key, index) pairs in LDS by the whole workgroup
+__device__ __forceinline__ void lk_bitonic(double* sk, int* si, int P) {
+  for (int sz = 2; sz <= P; sz <<= 1) {
+    for (int st = sz >> 1; st > 0; st >>= 1) {
+      for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
+        const int i = ((t & ~(st - 1)) << 1) | (t & (st - 1));
+        const int j = i | st;
+        const bool up = (i & sz) == 0;
+        const double ki = sk[i], kj = sk[j];
+        const int ii = si[i], ij = si[j];
+        const bool gt = ki > kj || (ki == kj && ii > ij);
+        if (gt == up) { sk[i] = kj; sk[j] = ki; si[i] = ij; si[j] = ii; }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// exact keys of m rows (row j: idx ? idx[j] : base + j) of g into sk[j] / si[j],
+// the workgroup's waves taking four rows per pass (exact_keys4*: the summation
+// order of exact_key, bit-identical keys; several gathers in flight per wave)
+template <int NI>
+__device__ __forceinline__ void lk_keys(const float* qr, const float* qreg, const float* __restrict__ g, int D,
+                                        int metric, const int* idx, int base, int m, double* sk, int* si) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  for (int j0 = wid * 4; j0 < m; j0 += nw * 4) {
+    const int n = min(4, m - j0);
+    int row[4];
+    const float* gr[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int j = j0 + (u < n ? u : 0);
+      row[u] = idx ? idx[j] : base + j;
+      gr[u] = g + (long long)row[u] * D;
+    }
+    double kk[4];
+    if (D <= 64 * NI)
+      exact_keys4_reg<NI>(qreg, gr, n, D, lane, metric, kk);
+    else
+      exact_keys4(qr, gr, n, D, lane, metric, kk);
+    if (lane == 0) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (u < n) { sk[j0 + u] = kk[u]; si[j0 + u] = row[u]; }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(512) knn_lk_select_kernel(const float* __restrict__ q, const float* __restrict__ g,
+                                                            int D, int n_g, int k, int metric, long long g_base,
+                                                            const int* __restrict__ col_n,
+                                                            const int* __restrict__ col_i, int cap, int allrows,
+                                                            long long* __restrict__ out_i,
+                                                            double* __restrict__ out_d, int* __restrict__ flag) {
+  __shared__ double sk[LK_SORT];
+  __shared__ int si[LK_SORT];
+  const int qi = blockIdx.x, lane = threadIdx.x & 63;
+  const int n = allrows ? n_g : col_n[qi];
+  if (!allrows && (n > cap || n < min(k, n_g))) {  // workgroup-uniform
+    if (threadIdx.x == 0) {
+      flag[qi] = 1;
+      atomicAdd(&g_knn_lk_stat[1], 1ull);
+    }
+    return;
+  }
+  if (threadIdx.x == 0) {
+    flag[qi] = 0;
+    atomicAdd(&g_knn_lk_stat[0], 1ull);
+  }
+  int P = 64;
+  while (P < n) P <<= 1;  // n <= cap <= LK_SORT
+  constexpr int NI = 8;
+  const float* qr = q + (long long)qi * D;
+  float qreg[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) qreg[i] = qr[min(lane + 64 * i, D - 1)];
+  lk_keys<NI>(qr, qreg, g, D, metric, allrows ? nullptr : col_i + (long long)qi * cap, 0, n, sk, si);
+  for (int c = n + threadIdx.x; c < P; c += blockDim.x) { sk[c] = INFINITY; si[c] = LK_PAD; }
+  __syncthreads();
+  lk_bitonic(sk, si, P);
+  for (int r = threadIdx.x; r < k; r += blockDim.x) {
+    const bool ok = r < n;
+    out_i[(long long)qi * k + r] = ok ? g_base + si[r] : -1;
+    out_d[(long long)qi * k + r] = ok ? sk[r] : INFINITY;
+  }
+}
+
+// exhaustive exact top-k of a flagged query, k <= 1024 (correct, not fast): one
+// workgroup streams the gallery in batches of 1024 rows; LDS holds the 1024 best
+// (key, index) so far and the batch's keys, and one sort of the 2048 keeps the best
+constexpr int LK_XB = 1024;
+__global__ void __launch_bounds__(1024) knn_lk_exhaustive_kernel(const float* __restrict__ q,
+                                                                 const float* __restrict__ g, int D, int n_g, int k,
+                                                                 int metric, long long g_base,
+                                                                 const int* __restrict__ flag,
+                                                                 long long* __restrict__ out_i,
+                                                                 double* __restrict__ out_d) {
+  const int qi = blockIdx.x;
+  if (!flag[qi]) return;
+  __shared__ double sk[2 * LK_XB];
+  __shared__ int si[2 * LK_XB];
+  const int lane = threadIdx.x & 63;
+  constexpr int NI = 8;
+  const float* qr = q + (long long)qi * D;
+  float qreg[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) qreg[i] = qr[min(lane + 64 * i, D - 1)];
+  for (int c = threadIdx.x; c < LK_XB; c += blockDim.x) { sk[c] = INFINITY; si[c] = LK_PAD; }
+  for (int base = 0; base < n_g; base += LK_XB) {
+    const int m = min(LK_XB, n_g - base);
+    lk_keys<NI>(qr, qreg, g, D, metric, nullptr, base, m, sk + LK_XB, si + LK_XB);
+    for (int c = m + threadIdx.x; c < LK_XB; c += blockDim.x) { sk[LK_XB + c] = INFINITY; si[LK_XB + c] = LK_PAD; }
+    __syncthreads();
+    lk_bitonic(sk, si, 2 * LK_XB);
+  }
+  __syncthreads();
+  for (int r = threadIdx.x; r < k; r += blockDim.x) {
+    const bool ok = si[r] != LK_PAD;
+    out_i[(long long)qi * k + r] = ok ? g_base + si[r] : -1;
+    out_d[(long long)qi * k + r] = ok ? sk[r] : INFINITY;
+  }
+}
+
+// out[qi][i] = exact key of (query qi, row i), every pair (one wave per key)
+__global__ void knn_exact_keys_kernel(const float* __restrict__ q, int nq, const float* __restrict__ g, long long n,
+                                      int D, int metric, double* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  for (int qi = blockIdx.y; qi < nq; qi += gridDim.y)
+    for (long long i = blockIdx.x * (long long)(blockDim.x / 64) + (threadIdx.x >> 6); i < n;
+         i += (long long)gridDim.x * (blockDim.x / 64)) {
+      const double d = exact_key(q + (long long)qi * D, g + i * D, D, lane, metric);
+      if (lane == 0) out[(long long)qi * n + i] = d;
+    }
+}
+
 // exact key of every query's positive when it lies in this shard's rows
 // [g_base, g_base + n), else -1 (one wave per query)
 __global__ void positive_key_kernel(const float* __restrict__ q, const float* __restrict__ g, int D, int nq,
@@ -1716,7 +1946,7 @@ extern "C" int artsbir_knn_scan(int dtype, const void* qc, const void* gc, const
   a.tiles_per_chunk = tiles_per_chunk;
   const int tiles = (ng + 127) / 128;
   a.nchunks = (tiles + tiles_per_chunk - 1) / tiles_per_chunk;
-  a.lo = lo; a.hi = hi; a.cnt = cnt; a.unc = unc; a.unc_cap = unc_cap; a.cand_d = cand_d; a.cand_i = cand_i;
+  a.lo = lo; a.hi = hi; a.cnt = cnt; a.unc = unc; a.unc_cap = unc_cap; a.cand_d = cand_d; a.cand_i = cand_i; a.col_n = nullptr; a.col_i = nullptr; a.col_cap = 0;
   const unsigned grid = (unsigned)(a.nchunks * ((nq + 127) / 128));
   if (dtype == ARTSBIR_DT_BF16)
     hipLaunchKernelGGL(knn_scan_kernel<bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
@@ -1785,7 +2015,7 @@ extern "C" int artsbir_knn_scan_aug(const void* qc, const void* ga, const float*
   a.tiles_per_chunk = tiles_per_chunk;
   const int tiles = (ng + 127) / 128;
   a.nchunks = (tiles + tiles_per_chunk - 1) / tiles_per_chunk;
-  a.lo = lo; a.hi = hi; a.cnt = cnt; a.unc = unc; a.unc_cap = unc_cap; a.cand_d = cand_d; a.cand_i = cand_i;
+  a.lo = lo; a.hi = hi; a.cnt = cnt; a.unc = unc; a.unc_cap = unc_cap; a.cand_d = cand_d; a.cand_i = cand_i; a.col_n = nullptr; a.col_i = nullptr; a.col_cap = 0;
   const unsigned grid = (unsigned)(a.nchunks * ((nq + 255) / 256));
   knn_scan_v2_launch(Dp, grid, a, 0, (hipStream_t)stream);
   ARTSBIR_CHECK_LAUNCH("knn_scan_aug");
@@ -1810,19 +2040,32 @@ std::vector<std::pair<hipEvent_t, hipEvent_t>> g_scan_ev;
 struct TopkPlan {
   int dtype, v2, Dp, tpc, nchunks, ncand, unc_cap;
   int ncand_alloc;  // candidate slots the workspace holds per query (>= ncand)
-  size_t off[20];
+  int large;        // k > TOPK_KMAX: the threshold / collect / select path
+  int cand_cap;     //   candidate buffer entries per query (C below)
+  int allrows;      //   N <= C: every row is a candidate, no cut and no collect pass
+  size_t off[24];
   size_t total;
 };
 constexpr int TOPK_KMAX = 64;
+constexpr int TOPK_KMAX_LARGE = 1024;
+// C, the per-query candidate capacity of the large-k path: 2 k + 2048 (<= LK_SORT).
+// The rows under the cut T + 2 eps are the k wanted ones, those between the k-th
+// and the T-th approximate value (few once the lists hold 2 k items, see `need`
+// below) and those within 2 eps above T: a count that grows with the gallery's
+// density at the cut, not with k.  Emulated on the CPU (bf16-rounded operands,
+// eps of query_eps, randn galleries up to 1M x 512, k up to 1000) the count stays
+// under 2 k + 2048; 4 k does not hold at k = 100.  A query past C is
+// answered by the exhaustive kernel, so C bounds memory and time, not correctness.
+int g_topk_cand_cap = 4096;  // a limit on C (artsbir_knn_set_cand_cap: tests force the fallback); LK_SORT = none
 int g_topk_unc_cap = 1 << 20;  // artsbir_knn_set_unc_cap (tests force the overflow path)
 
 enum { W_QSQ, W_GSQ, W_EXT, W_QEPS, W_QC, W_GC, W_LO, W_HI, W_DPOS, W_CNT, W_UNC, W_CD, W_CI, W_FLAG, W_PK, W_PI, W_KB,
-       W_HB, W_HIST, W_END };
+       W_HB, W_HIST, W_CTHR, W_COLN, W_COLI, W_END };
 
 int topk_plan(int dtype, int Q, long long N, int D, int k, int tpc_req, TopkPlan& p) {
-  if (Q < 0 || N < 1 || D < 1 || k < 1 || k > TOPK_KMAX || N > 0x7fffffffLL) {
-    set_error("pairwise_l2_topk: need Q >= 0, 1 <= N < 2^31, D >= 1, 1 <= k <= %d (Q=%d N=%lld D=%d k=%d)", TOPK_KMAX,
-              Q, N, D, k);
+  if (Q < 0 || N < 1 || D < 1 || k < 1 || k > TOPK_KMAX_LARGE || N > 0x7fffffffLL) {
+    set_error("pairwise_l2_topk: need Q >= 0, 1 <= N < 2^31, D >= 1, 1 <= k <= %d (Q=%d N=%lld D=%d k=%d)",
+              TOPK_KMAX_LARGE, Q, N, D, k);
     return -1;
   }
   if (dtype != ARTSBIR_DT_BF16 && dtype != ARTSBIR_DT_F32) { set_error("pairwise_l2_topk: dtype %d", dtype); return -1; }
@@ -1832,7 +2075,13 @@ int topk_plan(int dtype, int Q, long long N, int D, int k, int tpc_req, TopkPlan
   p.v2 = dtype == ARTSBIR_DT_BF16 && artsbir_knn_scan_aug_supported(p.Dp);
   const long long tiles = (N + 127) / 128;
   long long tpc = tpc_req > 0 ? tpc_req : (p.v2 ? 256 : 64);
-  const long long need = (k + KT - 1) / KT;           // chunks whose lists can hold k items
+  p.large = k > TOPK_KMAX;
+  p.cand_cap = std::min(2 * k + 2048, g_topk_cand_cap);
+  p.allrows = p.large && N <= p.cand_cap;
+  // chunks whose lists can hold k items; 2 k for the large-k path, whose cut is the
+  // k-th smallest of the lists' union: with twice the slots it lies close to the
+  // gallery's own k-th smallest and fewer rows pass it
+  const long long need = ((p.large ? 2 * k : k) + KT - 1) / KT;
   if (tiles / need < tpc) tpc = tiles / need > 0 ? tiles / need : 1;
   const long long maxch = 60000 / (KT * 12);          // knn_merge's shared memory
   if ((tiles + tpc - 1) / tpc > maxch) tpc = (tiles + maxch - 1) / maxch;
@@ -1886,7 +2135,9 @@ int topk_plan(int dtype, int Q, long long N, int D, int k, int tpc_req, TopkPlan
   sz[W_UNC] = 4 * (2 * (size_t)p.unc_cap + 1);
   sz[W_CD] = sz[W_CI] = 4 * (size_t)Q * p.ncand_alloc;
   sz[W_FLAG] = 4 * (size_t)Q;
-  sz[W_PK] = sz[W_PI] = 8 * (size_t)Q * W * k;
+  sz[W_PK] = sz[W_PI] = p.large ? 0 : 8 * (size_t)Q * W * k;  // knn_lk_exhaustive_kernel writes the outputs itself
+  sz[W_CTHR] = sz[W_COLN] = p.large ? 4 * (size_t)Q : 0;
+  sz[W_COLI] = p.large && !p.allrows ? 4 * (size_t)Q * p.cand_cap : 0;
   sz[W_KB] = 4 * (size_t)Q;
   sz[W_HB] = 4 * (size_t)Q;
   sz[W_HIST] = 4 * (size_t)Q * HB_BINS;
@@ -1992,12 +2243,13 @@ extern "C" int artsbir_pairwise_l2_topk(int dtype, int metric, const float* q, i
   }
   KnnScanArgs a;
   a.q = qc; a.g = gc; a.qsq = qsq; a.gsq = gsq; a.gsq_max = 0.f; a.gsq_max_p = reinterpret_cast<const float*>(ext);
-  a.thr0 = nullptr; a.kb = (p.v2 && kb_on) ? kbuf : nullptr; a.kq = k;
+  // the shared k-th bound and its histogram read the k-th entry of a KT-item list: off for large k
+  a.thr0 = nullptr; a.kb = (p.v2 && kb_on && !p.large) ? kbuf : nullptr; a.kq = k;
   a.hist = a.kb && hist_on ? hist : nullptr; a.hbase = a.hist ? hbase : nullptr; a.rel = rel; a.Nq = Q; a.Ng = ng; a.D = p.Dp;
   a.tiles_per_chunk = p.tpc;
   a.nchunks = p.nchunks;
   a.lo = positives ? lo : nullptr; a.hi = positives ? hi : nullptr;
-  a.cnt = cnt; a.unc = unc; a.unc_cap = p.unc_cap; a.cand_d = cand_d; a.cand_i = cand_i;
+  a.cnt = cnt; a.unc = unc; a.unc_cap = p.unc_cap; a.cand_d = cand_d; a.cand_i = cand_i; a.col_n = nullptr; a.col_i = nullptr; a.col_cap = 0;
   if (p.v2) {
     const unsigned grid = (unsigned)(p.nchunks * ((Q + 255) / 256));
     const int sstat = knn_stat_on() ? 1 : 0;
@@ -2015,8 +2267,32 @@ extern "C" int artsbir_pairwise_l2_topk(int dtype, int metric, const float* q, i
   ARTSBIR_CHECK_LAUNCH("pairwise_l2_topk scan");
   if (ev1) (void)hipEventRecord(ev1, st);
   const size_t sh = (size_t)p.ncand * (sizeof(double) + sizeof(int));
-  if (!launch_merge_wave(Q, st, q, g, D, p.nchunks, cand_d, cand_i, qsq, 0.f, rel, g_base, k, out_idx, out_dist, flag,
-                         metric, qeps, N))
+  if (p.large) {
+    // cut from the chunk lists -> collect pass over the same operands -> exact select
+    float* cthr = reinterpret_cast<float*>(w + p.off[W_CTHR]);
+    int* col_n = reinterpret_cast<int*>(w + p.off[W_COLN]);
+    int* col_i = reinterpret_cast<int*>(w + p.off[W_COLI]);
+    if (!p.allrows) {
+      if (hipMemsetAsync(col_n, 0, 4 * (size_t)Q, st) != hipSuccess) {
+        set_error("pairwise_l2_topk: memset failed");
+        return -2;
+      }
+      hipLaunchKernelGGL(knn_lk_thresh_kernel, dim3(Q), dim3(64), (size_t)p.ncand * 4, st, cand_d, cand_i, p.ncand, k,
+                         qeps, cthr);
+      KnnScanArgs c = a;
+      c.thr0 = cthr; c.kb = nullptr; c.hist = nullptr; c.hbase = nullptr; c.lo = nullptr; c.hi = nullptr;
+      c.col_n = col_n; c.col_i = col_i; c.col_cap = p.cand_cap;
+      if (p.v2)
+        knn_scan_v2_collect_launch(p.Dp, (unsigned)(p.nchunks * ((Q + 255) / 256)), c, st);
+      else if (dtype == ARTSBIR_DT_BF16)
+        hipLaunchKernelGGL((knn_scan_kernel<bf16, 1>), dim3((unsigned)(p.nchunks * ((Q + 127) / 128))), dim3(256), 0, st, c);
+      else
+        hipLaunchKernelGGL((knn_scan_kernel<float, 1>), dim3((unsigned)(p.nchunks * ((Q + 127) / 128))), dim3(256), 0, st, c);
+    }
+    hipLaunchKernelGGL(knn_lk_select_kernel, dim3(Q), dim3(512), 0, st, q, g, D, ng, k, metric, g_base, col_n, col_i,
+                       p.cand_cap, p.allrows, out_idx, out_dist, flag);
+  } else if (!launch_merge_wave(Q, st, q, g, D, p.nchunks, cand_d, cand_i, qsq, 0.f, rel, g_base, k, out_idx, out_dist,
+                                flag, metric, qeps, N))
     hipLaunchKernelGGL(knn_merge_kernel, dim3(Q), dim3(256), sh, st, q, g, D, p.nchunks, cand_d, cand_i, qsq, 0.f, rel,
                        g_base, k, out_idx, out_dist, flag, metric, qeps, N);
   if (positives) {
@@ -2027,10 +2303,15 @@ extern "C" int artsbir_pairwise_l2_topk(int dtype, int metric, const float* q, i
     hipLaunchKernelGGL(knn_count_exhaustive_kernel, dim3(2048), dim3(256), 0, st, q, g, D, N, unc + 2 * p.unc_cap,
                        p.unc_cap, dpos, positives, g_base, cnt, metric, Q);
   }
-  hipLaunchKernelGGL(knn_exact_topk_part_kernel, dim3(KNN_XB, Q), dim3(256), 0, st, q, g, D, N, k, metric, flag, pkey,
-                     pidx);
-  hipLaunchKernelGGL(topk_lists_merge_kernel, dim3(Q), dim3(256), (size_t)KNN_XB * 4 * k, st, pkey, pidx,
-                     KNN_XB * 4, k, (long long)KNN_XB * 4 * k, (long long)k, flag, g_base, out_idx, out_dist);
+  if (p.large) {
+    hipLaunchKernelGGL(knn_lk_exhaustive_kernel, dim3(Q), dim3(1024), 0, st, q, g, D, ng, k, metric, g_base, flag,
+                       out_idx, out_dist);
+  } else {
+    hipLaunchKernelGGL(knn_exact_topk_part_kernel, dim3(KNN_XB, Q), dim3(256), 0, st, q, g, D, N, k, metric, flag, pkey,
+                       pidx);
+    hipLaunchKernelGGL(topk_lists_merge_kernel, dim3(Q), dim3(256), (size_t)KNN_XB * 4 * k, st, pkey, pidx,
+                       KNN_XB * 4, k, (long long)KNN_XB * 4 * k, (long long)k, flag, g_base, out_idx, out_dist);
+  }
   if (out_rank) hipLaunchKernelGGL(rank_out_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, cnt, Q, out_rank);
   if (out_dpos && hipMemcpyAsync(out_dpos, dpos, 8 * (size_t)Q, hipMemcpyDeviceToDevice, st) != hipSuccess) {
     set_error("pairwise_l2_topk: dpos copy failed");
@@ -2098,4 +2379,36 @@ extern "C" int artsbir_knn_set_unc_cap(int cap) {
   const int old = g_topk_unc_cap;
   if (cap > 0) g_topk_unc_cap = cap;
   return old;
+}
+
+// upper limit of the candidate capacity C = 2 k + 2048 of the large-k path (default
+// LK_SORT: no limit); a small value forces the exhaustive fallback (tests).  Returns the old one.
+extern "C" int artsbir_knn_set_cand_cap(int cap) {
+  const int old = g_topk_cand_cap;
+  if (cap > 0) g_topk_cand_cap = cap < LK_SORT ? cap : LK_SORT;
+  return old;
+}
+
+extern "C" int artsbir_knn_largek_stat_read(long long* out2, int reset) {
+  unsigned long long v[2];
+  if (hipMemcpyFromSymbol(v, HIP_SYMBOL(g_knn_lk_stat), sizeof(v)) != hipSuccess) return -1;
+  out2[0] = (long long)v[0];
+  out2[1] = (long long)v[1];
+  if (reset) {
+    static const unsigned long long z[2] = {0, 0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_knn_lk_stat), z, sizeof(z)) != hipSuccess) return -1;
+  }
+  return 0;
+}
+
+extern "C" int artsbir_knn_exact_keys(int metric, const float* q, int Q, const float* g, long long N, int D,
+                                      double* out, void* stream) {
+  if (metric != 0 && metric != 1) { set_error("knn_exact_keys: metric %d (0 = euclidean, 1 = cosine)", metric); return -1; }
+  if (Q < 0 || N < 0 || D < 1) { set_error("knn_exact_keys: Q=%d N=%lld D=%d", Q, N, D); return -1; }
+  if (Q == 0 || N == 0) return 0;
+  const long long gx = std::min<long long>((N + 3) / 4, 16384);
+  hipLaunchKernelGGL(knn_exact_keys_kernel, dim3((unsigned)gx, (unsigned)std::min(Q, 4096)), dim3(256), 0,
+                     (hipStream_t)stream, q, Q, g, N, D, metric, out);
+  ARTSBIR_CHECK_LAUNCH("knn_exact_keys");
+  return 0;
 }

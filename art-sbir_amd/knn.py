@@ -23,7 +23,9 @@ import _hip
 from _hip import call, ptr
 
 METRICS = {"euclidean": 0, "cosine": 1}
-KMAX = 64
+KMAX = 64           # up to here the chunk lists are merged by one wave per query (the fast path)
+KMAX_LARGE = 1024   # up to here one library call (threshold / collect / select, include/artsbir.h)
+PLAIN_BYTES = 256 << 20  # k > KMAX_LARGE: bytes of exact keys ([Qb, N] f64) per query batch of the plain path
 
 
 def _s():
@@ -48,7 +50,13 @@ def knn(queries: torch.Tensor, gallery: torch.Tensor, k: int = 10, positives: to
     ||q - g + 1e-6|| (utils.py:42), "cosine" by 1 - cos (utils.py:31-40); dist
     holds that key.  With g_base / dpos this is one shard of a larger gallery
     (dpos: the exact key of positives living in other shards, -1 otherwise) and
-    a shard shorter than k pads with index -1 / distance +inf."""
+    a shard shorter than k pads with index -1 / distance +inf.
+
+    Any k >= 1 (k <= N unless this is a shard call).  k <= KMAX_LARGE is the one
+    library call.  Beyond it the plain path runs: every exact key
+    (artsbir_knn_exact_keys, query batches of PLAIN_BYTES) and a stable sort on
+    the key, which is the (key, index) order; rank and dpos then come from the
+    ordinary call with k clipped to KMAX_LARGE."""
     if not (queries.is_cuda and gallery.is_cuda):
         raise RuntimeError("knn on libartsbir_hip needs CUDA tensors")
     m = _metric(metric)
@@ -59,8 +67,10 @@ def knn(queries: torch.Tensor, gallery: torch.Tensor, k: int = 10, positives: to
     shard = g_base != 0 or dpos is not None
     if k > N and not shard:
         raise ValueError(f"k={k} > gallery size {N}")  # torch.topk(k) on N < k raises too
-    if not 1 <= k <= KMAX:
-        raise ValueError(f"k={k} outside 1..{KMAX}")
+    if k < 1:
+        raise ValueError(f"k={k} must be at least 1")
+    if k > KMAX_LARGE:
+        return _knn_plain(q, g, k, m, positives, compute, g_base, dpos, tiles_per_chunk, metric)
     dev = q.device
     dt = _hip.DT_BF16 if compute == "bf16" else _hip.DT_F32
     tpc = int(tiles_per_chunk or 0)
@@ -91,6 +101,31 @@ def knn(queries: torch.Tensor, gallery: torch.Tensor, k: int = 10, positives: to
     return out_i, out_d, rank, out_dp
 
 
+def _knn_plain(q, g, k, m, positives, compute, g_base, dpos, tiles_per_chunk, metric):
+    """k > KMAX_LARGE: all exact keys, stably sorted (see knn)"""
+    Q, D = q.shape
+    N = g.shape[0]
+    dev = q.device
+    rank = out_dp = None
+    if positives is not None:
+        _, _, rank, out_dp = knn(q, g, min(KMAX_LARGE, max(N, 1)), positives, compute, g_base, dpos, tiles_per_chunk,
+                                 metric)
+    out_i = torch.full((Q, k), -1, dtype=torch.int64, device=dev)
+    out_d = torch.full((Q, k), float("inf"), dtype=torch.float64, device=dev)
+    kk = min(k, N)
+    if kk == 0:
+        return out_i, out_d, rank, out_dp
+    qb = max(1, PLAIN_BYTES // (8 * N))
+    for q0 in range(0, Q, qb):
+        qs = q[q0:q0 + qb]
+        keys = torch.empty(qs.shape[0], N, dtype=torch.float64, device=dev)
+        call("artsbir_knn_exact_keys", m, ptr(qs), qs.shape[0], ptr(g), N, D, ptr(keys), _s())
+        sd, si = torch.sort(keys, dim=1, stable=True)
+        out_d[q0:q0 + qb, :kk] = sd[:, :kk]
+        out_i[q0:q0 + qb, :kk] = si[:, :kk] + g_base
+    return out_i, out_d, rank, out_dp
+
+
 def shard_positive_distances(queries, gallery_shard, g_base: int, positives, metric: str = "euclidean"):
     """f64 [Q]: the exact key of each query's positive if it lies in this shard's
     rows [g_base, g_base + n), -1 for the others (and for no positive)."""
@@ -104,8 +139,12 @@ def shard_positive_distances(queries, gallery_shard, g_base: int, positives, met
 
 
 def merge_topk_device(all_d: torch.Tensor, all_i: torch.Tensor, k: int):
-    """[nshard, Q, k] gathered lists -> global top-k by (distance, index) on the GPU"""
+    """[nshard, Q, k] gathered lists -> global top-k by (distance, index) on the GPU
+    (artsbir_topk_merge, nshard * k <= 65536; past that, and for k > KMAX_LARGE, the
+    host restatement merge_topk runs on the device tensors)"""
     ns, Q, _ = all_d.shape
+    if k > KMAX_LARGE or ns * k > 65536:
+        return merge_topk(list(all_i), list(all_d), k)
     out_i = torch.empty(Q, k, dtype=torch.int64, device=all_d.device)
     out_d = torch.empty(Q, k, dtype=torch.float64, device=all_d.device)
     call("artsbir_topk_merge", ns, Q, k, ptr(all_d.contiguous()), ptr(all_i.contiguous()), ptr(out_i), ptr(out_d),
@@ -134,7 +173,10 @@ def knn_sharded(queries, gallery_shard, g_base: int, k: int = 10, positives=None
     local search, all_gather of (k keys, k indices) per query, merge, and
     all_reduce(SUM) of the per-shard ranks.  local_search / positive_keys / merge
     default to the library (knn, shard_positive_distances, merge_topk_device);
-    the gloo tests substitute CPU stand-ins to run this same protocol code."""
+    the gloo tests substitute CPU stand-ins to run this same protocol code.
+    Any k: the local search is knn's (one call up to KMAX_LARGE, the plain path
+    beyond) and merge_topk_device merges on the device up to KMAX_LARGE, with the
+    host restatement merge_topk on the device tensors beyond."""
     import torch.distributed as dist
     local_search = local_search or knn
     positive_keys = positive_keys or shard_positive_distances

@@ -513,13 +513,18 @@ int artsbir_knn_exact_all(const float* q, const float* g, int D, int n, double* 
  *   positive (-1 if none).  dpos_in (nullable): for a shard call, the positive's
  *   key when it lives in another shard (artsbir_positive_key + a MAX all-reduce).
  * dtype: ARTSBIR_DT_BF16 (bf16 MFMA scan) or ARTSBIR_DT_F32 (f32 MFMA scan); the
- * result is exact either way.  1 <= k <= 64, N < 2^31.  tiles_per_chunk 0 = auto
+ * result is exact either way.  1 <= k <= 1024, N < 2^31: up to k = 64 the chunk
+ * lists are merged by one wave per query; for 65 <= k <= 1024 the lists give a
+ * per-query cut, a second scan pass collects every row under it (at most
+ * C = 2 k + 2048 per query) and one workgroup per query sorts their exact keys;
+ * outputs and semantics are the same.  tiles_per_chunk 0 = auto
  * (bf16: up to 256 tiles of 128 rows, shortened so the scan's ceil(Q/256) x
  * chunks workgroups fill whole rounds of the current device's CUs; the same
  * choice in the workspace query and the call on one device).
  * workspace: device memory of artsbir_pairwise_l2_topk_workspace() bytes.  No
  * host synchronisation; the rare fallbacks (uncertain-queue overflow, a chunk
- * list that may have hidden a top-k item) run as device kernels. */
+ * list that may have hidden a top-k item, more than C candidates) run as device
+ * kernels. */
 long long artsbir_pairwise_l2_topk_workspace(int dtype, int Q, long long N, int D, int k, int tiles_per_chunk);
 int artsbir_pairwise_l2_topk(int dtype, int metric, const float* q, int Q, const float* g, long long N, int D, int k,
                              const long long* positives, const double* dpos_in, long long g_base, int tiles_per_chunk,
@@ -528,6 +533,19 @@ int artsbir_pairwise_l2_topk(int dtype, int metric, const float* q, int Q, const
 /* capacity of its uncertain-item queue (default 2^20; a small value forces the
  * exhaustive recount fallback, for tests); returns the previous capacity. */
 int artsbir_knn_set_unc_cap(int cap);
+/* upper limit of the candidate capacity C of its large-k path (default 4096: C =
+ * 2 k + 2048 as is; a small value sends every query with more candidates to the
+ * exhaustive fallback, for tests); cap <= 0 changes nothing; returns the
+ * previous limit. */
+int artsbir_knn_set_cand_cap(int cap);
+/* out2 = {queries answered by the large-k select path, queries answered by its
+ * exhaustive fallback} since the last reset (counted on the device). */
+int artsbir_knn_largek_stat_read(long long* out2, int reset);
+/* out[q][i] = exact f64 key (metric 0 / 1 as artsbir_pairwise_l2_topk) of query q
+ * and gallery row i, out is [Q][N]: the plain path for k > 1024 (sort on the
+ * caller's side) and the metric-aware, multi-query form of artsbir_knn_exact_all. */
+int artsbir_knn_exact_keys(int metric, const float* q, int Q, const float* g, long long N, int D, double* out,
+                           void* stream);
 /* HIP-event timing of the scan kernel inside artsbir_pairwise_l2_topk (profiling):
  * on = 1 starts collecting, 0 stops; read returns the summed scan time and count. */
 int artsbir_scan_profile(int on);
