@@ -35,6 +35,18 @@ template <typename T> __device__ __forceinline__ T from_f(float x);
 template <> __device__ __forceinline__ float from_f<float>(float x) { return x; }
 template <> __device__ __forceinline__ bf16 from_f<bf16>(float x) { return (bf16)x; }
 
+// A Bottleneck's tail, one value (models.py:220-236): bn(y) = (y - mean) * scale
+// + beta of a [4][C] parameter block, out = relu(bn3(y3) + r).  The one
+// definition behind block_out_kernel / block_out_cg_kernel (elementwise.hip) and
+// bstream_kernel (bstream.hip), whose outputs must agree bit for bit (the same
+// expression tree, so the same FMA contraction in each)
+__device__ __forceinline__ float bn_value(float y, float mean, float scale, float beta) {
+  return (y - mean) * scale + beta;
+}
+__device__ __forceinline__ float block_out_value(float y3, float mean, float scale, float beta, float r) {
+  return fmaxf((y3 - mean) * scale + beta + r, 0.f);
+}
+
 // 16-byte vector of T: 8 x bf16 or 4 x f32
 template <typename T> struct Vec16;
 template <> struct Vec16<float> {

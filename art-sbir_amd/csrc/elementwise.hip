@@ -413,12 +413,12 @@ __global__ void block_out_kernel(const T* __restrict__ y3, const float* __restri
       load8<T>(yd + off, r);
       load_bn8(bnd + po, C, cg * 8, m2, s2, h2);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) r[e] = (r[e] - m2[e]) * s2[e] + h2[e];
+      for (int e = 0; e < 8; ++e) r[e] = bn_value(r[e], m2[e], s2[e], h2[e]);
     } else {
       load8<T>(idn + off, r);
     }
 #pragma unroll
-    for (int e = 0; e < 8; ++e) a[e] = fmaxf((a[e] - m[e]) * s[e] + h[e] + r[e], 0.f);
+    for (int e = 0; e < 8; ++e) a[e] = block_out_value(a[e], m[e], s[e], h[e], r[e]);
     store8<T>(out + off, a);
     if (bits) {  // ReLU mask of the stored values, one bit per channel
       unsigned m = 0;
@@ -474,10 +474,10 @@ __global__ void __launch_bounds__(256) block_out_cg_kernel(const T* __restrict__
       const long long row = base + rb + i * RL;
       if (yd) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) r[i][e] = (r[i][e] - m2[e]) * s2[e] + h2[e];
+        for (int e = 0; e < 8; ++e) r[i][e] = bn_value(r[i][e], m2[e], s2[e], h2[e]);
       }
 #pragma unroll
-      for (int e = 0; e < 8; ++e) a[i][e] = fmaxf((a[i][e] - m[e]) * sc[e] + h[e] + r[i][e], 0.f);
+      for (int e = 0; e < 8; ++e) a[i][e] = block_out_value(a[i][e], m[e], sc[e], h[e], r[i][e]);
       store8<T>(out + row * C + cg * 8, a[i]);
       if (bits) {
         unsigned mk = 0;

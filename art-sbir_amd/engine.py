@@ -78,6 +78,12 @@ FOLD_WG = [os.environ.get("ARTSBIR_FOLD_WG", "1") != "0"]
 # MFMA work on the side stream), which cost the C2 step more than the apply
 # pass it removes from the main stream (94.8 vs 91.2 ms on one box)
 FOLD_BN1 = [os.environ.get("ARTSBIR_FOLD_BN1", "0") == "1"]
+# a Bottleneck followed by another one leaves its tail (bn3 + residual + ReLU)
+# to the next block's conv1 forward (artsbir_block_out_conv1x1_fwd): one pass
+# writes the block output and feeds it to conv1, instead of block_out writing it
+# and the conv reading it back (bf16 training, atomic statistics; False: the two
+# launches)
+FUSE_BLOCK_CONV1 = [True]
 
 
 def set_deterministic(on: bool = True) -> bool:
@@ -592,10 +598,15 @@ class Engine:
         # residual stages (models.py:354-357)
         bctx = []
         blocks = m.blocks()
+        # the deterministic mode takes fixed-order statistics from the stored y1
+        fuse_tail = (FUSE_BLOCK_CONV1[0] and type(self) is Engine and train and self.dt == _hip.DT_BF16
+                     and not DETERMINISTIC)
+        tail = None
         for i, (blk, bp) in enumerate(zip(blocks, pk["blocks"])):
             # the next block's folded conv1 needs the column sums of its input
-            h, c, h_cs = self._block_fwd(blk, bp, h, train, stats, fold=fold, h_cs=h_cs,
-                                         out_cs=fold and self._fold1_on() and i + 1 < len(blocks))
+            out_cs = fold and self._fold1_on() and i + 1 < len(blocks)
+            h, c, h_cs, tail = self._block_fwd(blk, bp, h, train, stats, fold=fold, h_cs=h_cs, out_cs=out_cs, tail=tail,
+                                               defer=fuse_tail and not out_cs and i + 1 < len(blocks))
             bctx.append(c if save else None)
         ctx["blocks"] = bctx
 
@@ -619,12 +630,44 @@ class Engine:
         the column sums of the block input from the forward, like _fold_on)"""
         return FOLD_BN1[0] and self._fold_on()
 
-    def _block_fwd(self, blk, bp, h, train, stats, fold=False, h_cs=None, out_cs=False):
-        B, H, W, Cin = h.shape
-        s = blk.stride
+    def _tail_conv1(self, tail, blk, fw, stats):
+        """the previous block's deferred tail and this block's conv1 + bn1 statistics
+        in one call: returns the previous block's output (this block's input), y1
+        and bn1's state, and completes the previous block's saved context"""
+        y3, b3, yd, bd = tail["y3"], tail["b3"], tail["yd"], tail["bd"]
+        B, H, W, C = y3.shape
+        G = self._G
+        out = torch.empty_like(y3)
+        bits = None
+        if _fuse_bnb() and MASK_BITS:
+            bits = torch.empty(out.numel() // 8, dtype=torch.uint8, device=out.device)
+        cout = blk.conv1.weight.shape[0]
+        sb = stats.take(cout * G)
+        y1 = self._empty(B, H, W, cout, device=out.device)
+        d = self._desc(B, H, W, C, cout, 1, 1, 1, 0)
+        es = out.element_size()
+        # algorithmic: y3, the second operand and out once, the bits, W, y1
+        nbytes = float(es * (B * H * W * C * 3 + cout * C + B * H * W * cout)
+                       + (B * H * W * C // 8 if bits is not None else 0))
+        call("artsbir_block_out_conv1x1_fwd", d, ptr(y3), ptr(b3.block), ptr(yd), ptr(bd.block) if bd else None,
+             None if yd is not None else ptr(tail["h"]), ptr(fw), G, ptr(out),
+             bits.data_ptr() if bits is not None else None, ptr(y1), ptr(sb), _s(), kernel="auto",
+             flops=2.0 * B * H * W * cout * C, nbytes=nbytes, tag=f"fwd {B}x{H}x{W}x{C}->{cout} 1x1/1 +block_out")
+        tail["ctx"]["out"], tail["ctx"]["bits"] = out, bits
+        return out, y1, self._bn(blk.bn1, sb, (B // G) * H * W, True)
+
+    def _block_fwd(self, blk, bp, h, train, stats, fold=False, h_cs=None, out_cs=False, tail=None, defer=False):
+        """one Bottleneck.  tail: the previous block's deferred tail (h is None: it
+        comes out of the fused call); defer: leave this block's own tail to the
+        next block.  Returns (out, ctx, out column sums, deferred tail)."""
         # BN+ReLU outputs are materialised once (bf16): cheaper than re-applying
         # them in every GEMM tile that reads them (9 taps x N-tiles for 3x3)
-        y1, b1 = self._conv_bn(Act(h), blk.conv1, blk.bn1, bp["conv1"][0], 1, 0, train, stats)
+        if tail is not None:
+            h, y1, b1 = self._tail_conv1(tail, blk, bp["conv1"][0], stats)
+        else:
+            y1, b1 = self._conv_bn(Act(h), blk.conv1, blk.bn1, bp["conv1"][0], 1, 0, train, stats)
+        B, H, W, Cin = h.shape
+        s = blk.stride
         a1 = self._act_pool(y1, b1, 1, 0)
         y2, b2 = self._conv_bn(Act(a1), blk.conv2, blk.bn2, bp["conv2"][0], 1, 1, train, stats)
         cs2 = csd = None
@@ -646,6 +689,10 @@ class Engine:
                 din = h
                 csd = h_cs
             yd, bd = self._conv_bn(Act(din), blk.downsample[1], blk.downsample[2], bp["down"][0], 1, 0, train, stats)
+        ctx = dict(h=h, y1=y1, a1=a1, y2=y2, p2=p2, y3=y3, yd=yd, pd=pd, out=None, bits=None, b1=b1, b2=b2, b3=b3,
+                   bd=bd, cs2=cs2, csd=csd, h_cs=h_cs)
+        if defer:  # out and bits are written, and entered here, by the next block's _tail_conv1
+            return None, ctx, None, dict(y3=y3, b3=b3, yd=yd, bd=bd, h=h, ctx=ctx)
         out = torch.empty_like(y3)
         G = self._G
         Bs = B // G
@@ -663,9 +710,8 @@ class Engine:
              kernel="block_out_kernel", nbytes=float(out.element_size() * rows * G * C * 3 + (rows * G * C // 8 if bits
                                                                                                   is not None else 0)),
              tag=f"block_out {rows * G}x{C}{' +colsum' if ocs is not None else ''}")
-        ctx = dict(h=h, y1=y1, a1=a1, y2=y2, p2=p2, y3=y3, yd=yd, pd=pd, out=out, bits=bits, b1=b1, b2=b2, b3=b3,
-                   bd=bd, cs2=cs2, csd=csd, h_cs=h_cs)
-        return out, ctx, ocs
+        ctx["out"], ctx["bits"] = out, bits
+        return out, ctx, ocs, None
 
     def _attnpool_fwd(self, ap, pk, h):
         B, Hs, Ws, C = h.shape
@@ -1423,7 +1469,7 @@ class ModuleEngine(Engine):
         if hasattr(m, "conv3"):
             nbn = sum(b.num_features for b in m.modules() if isinstance(b, torch.nn.BatchNorm2d))
             stats = _Arena(torch.zeros(max(2 * NSLOT * nbn, 1), dtype=torch.float32, device=x.device), NSLOT * 2)
-            out, c, _ = self._block_fwd(m, pk, h, train, stats)
+            out, c, _, _ = self._block_fwd(m, pk, h, train, stats)
             return out.permute(0, 3, 1, 2).float().contiguous(), {"train": train, "c": c}
         out, c = self._attnpool_fwd(m, pk, h)
         return out.float(), {"train": train, "c": c}

@@ -105,6 +105,19 @@ int artsbir_conv2d_dgrad(const artsbir_conv_desc* d, const void* dy, const void*
 int artsbir_conv2d_fwd_seg(const artsbir_conv_desc* d, const void* x, const void* w, void* y, int nseg,
                            float* stats, void* stream);
 
+/* A Bottleneck's tail and the next block's conv1 forward in one pass
+ * (models.py:220-236, then models.py:198-199 of the following block):
+ * artsbir_block_out_mask (out, mask_bits: optional) followed by
+ * artsbir_conv2d_fwd_seg of `out` (y1, stats: optional), with the same results.
+ * d: the consumer conv1 (1x1, stride 1; C = the block's output channels, x =
+ * out [N][H][W][C]); y3 / bn3 / yd / bnd / identity as artsbir_block_out; w
+ * [Cout][C].  bf16 with (C, Cout) = (256, 64), (256, 128) or (512, 128) and
+ * segments of whole 16-pixel blocks run one streaming kernel that never reads
+ * `out` back (csrc/bstream.hip); anything else runs the two launches. */
+int artsbir_block_out_conv1x1_fwd(const artsbir_conv_desc* d, const void* y3, const float* bn3, const void* yd,
+                                  const float* bnd, const void* identity, const void* w, int nseg, void* out,
+                                  unsigned char* mask_bits, void* y1, float* stats, void* stream);
+
 /* y = act(conv(x) + bias[n] (+ res[m][n])), act = ReLU if relu (res_mode 0 / 1).
  * Eval-mode Conv2d + BatchNorm2d + ReLU (+ the Bottleneck's residual add) of
  * models.py:198-236 in one launch, the BatchNorm folded into w and bias by
