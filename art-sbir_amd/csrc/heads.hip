@@ -69,11 +69,13 @@ __global__ void ce_fwd_kernel(const float* __restrict__ logits, const long long*
     float s = 0.f;
     for (int c = lane; c < C; c += 64) s += expf(x[c] - m);
     s = warp_sum(s);
-    const float lse = m + logf(s);
-    for (int c = lane; c < C; c += 64) prob[(long long)r * C + c] = expf(x[c] - lse);
+    // log-softmax as (x - m) - log(sum): m + log(sum) rounded to f32 first would carry
+    // half an ulp of m (4e-6 at m = 80) into every probability of the row and the loss
+    const float ls = logf(s);
+    for (int c = lane; c < C; c += 64) prob[(long long)r * C + c] = expf((x[c] - m) - ls);
     const long long lab = labels[r];
     if (lab != ignore_index) {
-      total += lse - x[lab];
+      total += ls - (x[lab] - m);
       ++cnt;
     }
   }

@@ -4,6 +4,13 @@ Drop-in for torch.optim.Adam(params, lr, weight_decay) as used at train.py:158:
 coupled L2 (grad += weight_decay*param), betas (0.9, 0.999), eps 1e-8, no
 amsgrad, bias corrections 1-beta^step; same per-parameter state keys
 (``step``, ``exp_avg``, ``exp_avg_sq``) so optimizer state_dicts interchange.
+
+One deviation: the single launch applies one bias correction to a whole parameter
+group, so every parameter of a group that has a gradient must be at the same step.
+A parameter without ``.grad`` is skipped and gets no state, as in torch; but one
+that receives its first gradient after the others have stepped, which torch would
+start at its own step 1, raises RuntimeError ("parameters of one group are at
+different Adam steps").  Put such parameters into a group of their own.
 """
 from __future__ import annotations
 

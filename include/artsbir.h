@@ -586,7 +586,10 @@ int artsbir_linear_fwd(const float* x, const float* W, const float* bias, int B,
 /* dx = dy W; dW += dy^T x; db += colsum(dy). */
 int artsbir_linear_bwd(const float* dy, const float* x, const float* W, int B, int D, int C, float* dx, float* dW,
                        float* db, void* stream);
-/* nn.CrossEntropyLoss(reduction='mean', ignore_index): loss2 = {loss, #counted}; prob saved. */
+/* nn.CrossEntropyLoss(reduction='mean', ignore_index): loss2 = {loss, #counted}; prob saved.
+ * Deviation: when every row is ignored (#counted == 0) torch divides 0 by 0 and returns
+ * NaN; here the loss is 0 (the sum over no rows divided by 1).  The gradient is all
+ * zeros in both.  Labels other than ignore_index must lie in [0, C): they index the row. */
 int artsbir_cross_entropy_fwd(const float* logits, const long long* labels, int B, int C, long long ignore_index,
                               float* prob, float* loss2, void* stream);
 int artsbir_cross_entropy_bwd(const float* prob, const long long* labels, int B, int C, long long ignore_index,

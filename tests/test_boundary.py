@@ -52,6 +52,33 @@ def test_capi_rejects_bad_shapes_without_touching_the_gpu():
         _hip.call("artsbir_gemm_nt", _hip.DT_BF16, 16, 16, 12, None, 12, None, None, 16, 0, 0, None, None, None)
 
 
+def test_tail_entry_points_reject_bad_arguments_without_touching_the_gpu():
+    """attention pool, tokens, distances and Adam: every argument check sits ahead of
+    the launch, so NULL pointers are never read"""
+    import _hip
+    lib = _hip.lib()
+
+    def refused(name, *args):
+        assert getattr(lib, name)(*args) != 0, name
+        return lib.artsbir_last_error()
+
+    for dt in (_hip.DT_F32, _hip.DT_BF16):
+        for T, msg in ((0, b"tokens=0 outside [1,128]"), (129, b"tokens=129 outside [1,128]")):
+            assert msg in refused("artsbir_attnpool_fwd", dt, None, None, 2, 128, 2, T, None, None, None)
+            assert msg in refused("artsbir_attnpool_bwd", dt, None, None, None, None, 2, 128, 2, T, None, None, None)
+        msg = b"head_dim must be 64 (C=100 heads=2)"  # C != 64 * heads
+        assert msg in refused("artsbir_attnpool_fwd", dt, None, None, 2, 100, 2, 5, None, None, None)
+        assert msg in refused("artsbir_attnpool_bwd", dt, None, None, None, None, 2, 100, 2, 5, None, None, None)
+        assert b"tokens_fwd: C % 8" in refused("artsbir_tokens_fwd", dt, None, None, 2, 4, 12, None, None)
+        assert b"tokens_bwd: C % 8" in refused("artsbir_tokens_bwd", dt, None, 2, 4, 12, None, None)
+        assert b"tokens_bwd_ex: C % 8" in refused("artsbir_tokens_bwd_ex", dt, None, None, 2, 4, 12, None, None)
+    assert b"cosine: shapes 3 vs 5" in refused("artsbir_cosine_fwd", None, 3, None, 5, 8, 1e-8, None, None, None)
+    assert b"pairwise_l2: shapes 3 vs 5" in refused("artsbir_pairwise_l2", None, 3, None, 5, 8, 1e-6, None, None)
+    assert b"step must be >= 1" in refused("artsbir_adam_step", None, None, 1, 4096, 1e-3, 0.9, 0.999, 1e-8, 0.0, 0, None)
+    with pytest.raises(_hip.HipError, match="attnpool"):
+        _hip.call("artsbir_attnpool_fwd", _hip.DT_F32, None, None, 2, 128, 2, 129, None, None, None)
+
+
 @pytest.mark.parametrize("output_dim,count", [(1024, 38_316_896), (512, 37_267_808)])
 def test_modified_resnet_signature_keys_and_counts(output_dim, count):
     import models

@@ -32,8 +32,11 @@ def _pair(kind, seed):
     return mine, ref.double()
 
 
-KINDS = [("block", 64, 16, 1), ("block", 64, 32, 2), ("block", 128, 32, 1), ("pool", 4, 512, 8, 64)]
-IDS = ["block-proj", "block-stride2", "block-identity", "attnpool"]
+KINDS = [("block", 64, 16, 1), ("block", 64, 32, 2), ("block", 128, 32, 1), ("pool", 4, 512, 8, 64),
+         # token counts past the 64 a lane's first token covers (T = 65, 82, 122), and T = 2 with three heads
+         ("pool", 8, 512, 8, 64), ("pool", 9, 512, 8, 64), ("pool", 11, 512, 8, 64), ("pool", 1, 192, 3, 32)]
+IDS = ["block-proj", "block-stride2", "block-identity", "attnpool", "attnpool-T65", "attnpool-T82", "attnpool-T122",
+       "attnpool-T2-3heads"]
 
 
 @pytest.mark.parametrize("kind", KINDS, ids=IDS)
