@@ -12,13 +12,15 @@
 //   e  = k W,                                                k = -c1 (c2 - c3 istd mean)
 //   dW = diag(c1) g^T x + diag(b') W (x^T x) + k (1^T x)
 // so dy never exists: the data gradient is one GEMM over [g | x]
-// (artsbir_conv1x1_dgrad_fold, gemm.hip) with the weights this file prepares,
-// and the weight gradient is g^T x, the Gram matrix x^T x and the column sums of
-// x per segment, combined here.  That removes the BN-backward apply pass (read
-// g, y; write dy) and the data gradient's read of dy from the HBM-bound main
-// stream of the step.
+// (artsbir_conv1x1_dgrad_fold below, on the launcher of gemm.hip) with the
+// weights this file prepares, and the weight gradient is g^T x, the Gram matrix
+// x^T x and the column sums of x per segment, combined here.  That removes the
+// BN-backward apply pass (read g, y; write dy) and the data gradient's read of
+// dy from the HBM-bound main stream of the step.
+#include <cstdlib>
+
 #include "common.h"
-#include "../../include/artsbir.h"
+#include "conv_launch.h"
 
 namespace artsbir {
 
@@ -342,5 +344,233 @@ extern "C" int artsbir_bn_fold_wgrad_combine_y(int Co, int Ci, int nseg, const f
                      P, Q, (long long)Ci, (long long)Co * Ci, colsums, cs_slots < 1 ? 1 : cs_slots, Co, Ci, nseg, coef,
                      prm, pstride, dw);
   ARTSBIR_CHECK_LAUNCH("fold_wgrad_combine_y");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Data gradient of a 1x1 convolution with the BatchNorm backward of its output
+// folded in (artsbir.h: artsbir_conv1x1_dgrad_fold).  The reference's chain
+// conv -> BatchNorm2d (models.py:219-220 conv3 -> bn3, 227-229 downsample conv ->
+// BN) is differentiated by autograd as dy = c1 (g - c2 - xhat c3) followed by
+// dx = dy W; since y = x W^T the whole chain is linear in (g, x):
+//   dx = g (diag(c1) W) + x (W^T diag(b') W) + e,  b' = -c1 c3 istd,
+//   e = (-c1 (c2 - c3 istd mean)) W
+// per BN segment, so it runs as ONE GEMM over the concatenated reduction
+// [g | x] (K = Co + Ci) with per-segment weights (artsbir_bn_fold_bwd_prep) and
+// bias — no dy tensor is written or read.
+// ---------------------------------------------------------------------------
+template <typename T>
+__global__ void __launch_bounds__(256) fold_concat_kernel(const T* __restrict__ g, const T* __restrict__ x, T* out,
+                                                          long long M, int Co, int C2) {
+  constexpr int EPC = 16 / sizeof(T);
+  const int cg = (Co + C2) / EPC;  // 16-B chunks per output row
+  const long long n = M * cg;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const long long m = i / cg;
+    const int c = (int)(i - m * cg) * EPC;
+    const uint4 v = c < Co ? *reinterpret_cast<const uint4*>(g + m * Co + c)
+                           : *reinterpret_cast<const uint4*>(x + m * C2 + (c - Co));
+    *reinterpret_cast<uint4*>(out + m * (Co + C2) + c) = v;
+  }
+}
+
+// One fold launch: dx [N][H][W][Ci] = [g | x2] w_s^T + bias_s (+ residual) for
+// the pixels of BN segment s, g with Co channels, x2 with C2 (the conv input x,
+// C2 = Ci: artsbir_conv1x1_dgrad_fold; the BN input y, C2 = Co:
+// artsbir_conv1x1_dgrad_fold_y), an optional fused BN-backward reduction of the
+// gradient it produces
+struct FoldOp {
+  const artsbir_conv_desc* d;
+  const void* g;
+  const void* x2;
+  int C2;
+  const void* w;
+  const float* bias;
+  void* dx;
+  const void* res;
+  int res_mode;
+  const artsbir_bn_bwd_desc* bnb;
+  int nseg;
+  long long pstride;
+};
+
+static int fold_check(const FoldOp& f) {
+  const artsbir_conv_desc* d = f.d;
+  if (check_conv(d)) return -1;
+  if (d->R != 1 || d->S != 1 || d->stride != 1 || d->pad != 0) { set_error("conv1x1_dgrad_fold: 1x1 stride-1 convolutions only"); return -1; }
+  if (!f.g || !f.x2 || !f.w || !f.bias || !f.dx) { set_error("conv1x1_dgrad_fold: null operand"); return -1; }
+  if (d->Cout % 8 || d->C % 8 || f.C2 % 8 || f.C2 <= 0) { set_error("conv1x1_dgrad_fold: channels must be multiples of 8"); return -1; }
+  if (f.nseg < 1 || d->N % f.nseg) { set_error("conv1x1_dgrad_fold: %d segments do not divide batch %d", f.nseg, d->N); return -1; }
+  if (f.res_mode < 0 || f.res_mode > 2 || (f.res_mode && !f.res)) { set_error("conv1x1_dgrad_fold: bad residual"); return -1; }
+  if (f.res_mode == 2 && (d->H % 2 || d->W % 2)) { set_error("conv1x1_dgrad_fold: unpool residual needs even H, W"); return -1; }
+  if (f.res_mode == 2 && (d->N / f.nseg) * d->H * d->W % 4) { set_error("conv1x1_dgrad_fold: unpool residual segments"); return -1; }
+  if (const artsbir_bn_bwd_desc* b = f.bnb) {
+    if (b->dtype != d->dtype || b->pool > 1) { set_error("conv1x1_dgrad_fold: bad fused BN backward"); return -1; }
+    if (b->kind == 1) {
+      if (b->ntarget != 1 || !b->mask_bn || f.res_mode) {
+        set_error("conv1x1_dgrad_fold: a kind-1 fused BN backward takes one target and no residual");
+        return -1;
+      }
+    } else if (b->kind == 0 || b->kind == 3) {
+      if (b->ntarget < 1 || b->ntarget > 2 || !b->mask || !f.res_mode) {
+        set_error("conv1x1_dgrad_fold: a kind-0/3 fused BN backward takes 1-2 targets, a mask and a residual");
+        return -1;
+      }
+      if (b->kind == 3 && (d->dtype != ARTSBIR_DT_BF16 || d->C % 8)) { set_error("conv1x1_dgrad_fold: bit masks need bf16"); return -1; }
+    } else {
+      set_error("conv1x1_dgrad_fold: fused BN-backward kind %d", b->kind);
+      return -1;
+    }
+  }
+  return 0;
+}
+
+// the two-operand / per-segment-weight launch arguments of the fold (f passed
+// fold_check): the 1x1 data gradient over g, the reduction extended by x2
+static ConvArgs fold_conv_args(const FoldOp& f) {
+  const int Co = f.d->Cout, Ci = f.d->C, K = Co + f.C2;
+  artsbir_conv_desc t = *f.d;
+  t.C = Co; t.Cout = Ci;
+  ConvArgs a = conv_args_nhwc(&t, f.g, f.w, f.dx);
+  a.x2 = f.x2; a.sW2 = f.C2; a.sH2 = (long long)t.W * f.C2; a.sN2 = (long long)t.H * t.W * f.C2; a.x2_elems = a.M * f.C2;
+  a.C1 = Co; a.C = K; a.K = K;
+  a.bias = f.bias; a.res = f.res; a.res_mode = f.res_mode;
+  a.nseg = f.nseg; a.bnb_desc = f.bnb; a.bnb_pstride = f.pstride;
+  a.w_sstride = (long long)Ci * K; a.bias_sstride = Ci;
+  return a;
+}
+
+// segment s's slice of a fold launch (one BN segment, its weights and bias)
+static ConvArgs fold_segment(const FoldOp& f, const ConvArgs& a, int s, artsbir_bn_bwd_desc* bs) {
+  const int Co = f.d->Cout, Ci = f.d->C;
+  const long long seg_m = a.M / f.nseg;
+  const long long es = f.d->dtype == ARTSBIR_DT_BF16 ? 2 : 4;
+  ConvArgs p = a;
+  if (f.bnb) { *bs = bnb_segment(f.bnb, s, seg_m, Ci, f.pstride); p.bnb_desc = bs; }
+  p.nseg = 1; p.M = seg_m;
+  p.x = reinterpret_cast<const char*>(f.g) + s * seg_m * Co * es; p.x_elems = seg_m * Co;
+  p.x2 = reinterpret_cast<const char*>(f.x2) + s * seg_m * f.C2 * es; p.x2_elems = seg_m * f.C2;
+  p.w = reinterpret_cast<const char*>(f.w) + s * a.w_sstride * es;
+  p.bias = f.bias + s * Ci;
+  p.y = reinterpret_cast<char*>(f.dx) + s * seg_m * Ci * es;
+  if (f.res_mode) p.res = reinterpret_cast<const char*>(f.res) + s * (f.res_mode == 2 ? seg_m / 4 : seg_m) * Ci * es;
+  return p;
+}
+
+// the two operands concatenated per pixel into ws, then one plain GEMM per segment
+static int fold_concat_gemms(const FoldOp& f, const ConvArgs& a, void* ws, hipStream_t st) {
+  const artsbir_conv_desc* d = f.d;
+  const int Co = d->Cout, K = Co + f.C2;
+  const long long M = (long long)d->N * d->H * d->W, seg_m = M / f.nseg;
+  const bool bf = d->dtype == ARTSBIR_DT_BF16;
+  const long long es = bf ? 2 : 4;
+  {
+    const long long n = M * (K * es / 16);
+    const unsigned grid = (unsigned)((n + 255) / 256 < 65536 ? (n + 255) / 256 : 65536);
+    if (bf)
+      hipLaunchKernelGGL(fold_concat_kernel<bf16>, dim3(grid), dim3(256), 0, st, reinterpret_cast<const bf16*>(f.g),
+                         reinterpret_cast<const bf16*>(f.x2), reinterpret_cast<bf16*>(ws), M, Co, f.C2);
+    else
+      hipLaunchKernelGGL(fold_concat_kernel<float>, dim3(grid), dim3(256), 0, st, reinterpret_cast<const float*>(f.g),
+                         reinterpret_cast<const float*>(f.x2), reinterpret_cast<float*>(ws), M, Co, f.C2);
+    ARTSBIR_CHECK_LAUNCH("fold_concat");
+  }
+  for (int s = 0; s < f.nseg; ++s) {
+    artsbir_bn_bwd_desc bs;
+    ConvArgs p = fold_segment(f, a, s, &bs);
+    p.x2 = nullptr; p.C1 = 0; p.w_sstride = 0; p.bias_sstride = 0;
+    p.x = reinterpret_cast<const char*>(ws) + s * seg_m * K * es; p.x_elems = seg_m * K;
+    p.sW = K; p.sH = (long long)d->W * K; p.sN = (long long)d->H * d->W * K;
+    if (conv_launch(d->dtype, p, st)) return -1;
+  }
+  return 0;
+}
+
+static int fold_dgrad(const FoldOp& f, hipStream_t st) {
+  if (fold_check(f)) return -1;
+  const artsbir_conv_desc* d = f.d;
+  const ConvArgs a = fold_conv_args(f);
+  // one launch over every segment, else one per segment (the tiles of a
+  // launch then never straddle two), on the two-operand pipelined kernels
+  if (d->dtype == ARTSBIR_DT_BF16) {
+    int rc = conv_launch(ARTSBIR_DT_BF16, a, st);
+    if (rc <= 0) return rc;
+    // no kernel took the whole batch (a tile would straddle two segments): one
+    // launch per segment; segment 0 decides, a refusal there drops to the
+    // concatenated form below (every segment has the same shape)
+    for (int s = 0; s < f.nseg; ++s) {
+      artsbir_bn_bwd_desc bs;
+      const ConvArgs p = fold_segment(f, a, s, &bs);
+      rc = conv_launch(ARTSBIR_DT_BF16, p, st);
+      if (rc < 0) return rc;
+      if (rc > 0) {
+        if (s > 0) { set_error("conv1x1_dgrad_fold: segment %d has no kernel", s); return -1; }
+        break;
+      }
+    }
+    if (rc == 0) return 0;
+  }
+  // f32 (the parity mode) and shapes the pipelined kernels do not take: the two
+  // operands concatenated per pixel, then one plain GEMM per segment.  The
+  // concatenated operand is stream-ordered scratch (hipMallocAsync / hipFreeAsync
+  // on the caller's stream): no process-wide buffer shared across devices or
+  // threads, no device-synchronous hipFree in the middle of a step
+  const size_t need = (size_t)(a.M * a.K * (d->dtype == ARTSBIR_DT_BF16 ? 2 : 4));
+  void* ws = nullptr;
+  if (hipMallocAsync(&ws, need, st) != hipSuccess) {
+    set_error("conv1x1_dgrad_fold: workspace of %zu bytes", need);
+    return -1;
+  }
+  const int rc = fold_concat_gemms(f, a, ws, st);
+  (void)hipFreeAsync(ws, st);
+  return rc;
+}
+
+extern "C" int artsbir_conv1x1_dgrad_fold(const artsbir_conv_desc* d, const void* g, const void* x, const void* w,
+                                          const float* bias, void* dx, const artsbir_bn_bwd_desc* bnb, int nseg,
+                                          long long param_stride, void* stream) {
+  if (bnb && bnb->kind != 1) { set_error("conv1x1_dgrad_fold: the fused BN backward must be kind 1 with one target"); return -1; }
+  const FoldOp f{d, g, x, d ? d->C : 0, w, bias, dx, nullptr, 0, bnb, nseg, param_stride};
+  return fold_dgrad(f, (hipStream_t)stream);
+}
+
+extern "C" int artsbir_conv1x1_dgrad_fold_y(const artsbir_conv_desc* d, const void* g, const void* y, const void* w,
+                                            const float* bias, void* dx, const void* res, int res_mode,
+                                            const artsbir_bn_bwd_desc* bnb, int nseg, long long param_stride,
+                                            void* stream) {
+  const FoldOp f{d, g, y, d ? d->Cout : 0, w, bias, dx, res, res_mode, bnb, nseg, param_stride};
+  return fold_dgrad(f, (hipStream_t)stream);
+}
+
+// The fold's data gradient and, from the same pass, the operands of its weight
+// gradient (artsbir.h: artsbir_conv1x1_dgrad_fold_wg): per segment s
+// P[s] += g_s^T x_s ([Co][Ci]) and gram[s] += x_s^T x_s ([Ci][Ci]), f32.  One
+// kernel where pg_fold_wg_launch takes the shape; otherwise the data gradient
+// (artsbir_conv1x1_dgrad_fold) and one artsbir_gemm_tn2 per segment.
+extern "C" int artsbir_conv1x1_dgrad_fold_wg(const artsbir_conv_desc* d, const void* g, const void* x, const void* w,
+                                             const float* bias, void* dx, const artsbir_bn_bwd_desc* bnb, int nseg,
+                                             long long param_stride, float* P, float* gram, void* stream) {
+  if (bnb && bnb->kind != 1) { set_error("conv1x1_dgrad_fold_wg: the fused BN backward must be kind 1"); return -1; }
+  const FoldOp f{d, g, x, d ? d->C : 0, w, bias, dx, nullptr, 0, bnb, nseg, param_stride};
+  if (fold_check(f)) return -1;
+  if (!P || !gram) { set_error("conv1x1_dgrad_fold_wg: null weight-gradient operand"); return -1; }
+  const int Co = d->Cout, Ci = d->C;
+  const long long M = (long long)d->N * d->H * d->W, seg_m = M / nseg;
+  const long long es = d->dtype == ARTSBIR_DT_BF16 ? 2 : 4;
+  static const bool off = getenv("ARTSBIR_FOLD_WG") && atoi(getenv("ARTSBIR_FOLD_WG")) == 0;  // measurement switch
+  if (d->dtype == ARTSBIR_DT_BF16 && !off) {
+    ConvArgs a = fold_conv_args(f);
+    a.wg_p = P; a.wg_gram = gram;
+    const int rc = conv_launch(ARTSBIR_DT_BF16, a, (hipStream_t)stream);
+    if (rc <= 0) return rc;
+  }
+  if (artsbir_conv1x1_dgrad_fold(d, g, x, w, bias, dx, bnb, nseg, param_stride, stream)) return -1;
+  for (int s = 0; s < nseg; ++s) {
+    const char* gs = reinterpret_cast<const char*>(g) + s * seg_m * Co * es;
+    const char* xs = reinterpret_cast<const char*>(x) + s * seg_m * Ci * es;
+    if (artsbir_gemm_tn2(d->dtype, seg_m, Co, Ci, Ci, gs, Co, xs, Ci, xs, Ci, P + (long long)s * Co * Ci,
+                         gram + (long long)s * Ci * Ci, stream))
+      return -1;
+  }
   return 0;
 }

@@ -25,10 +25,46 @@ static void write_file(const char* path, const char* text) {
   fclose(f);
 }
 
+static char* read_file(const char* path, long* n) {
+  FILE* f = fopen(path, "rb");
+  if (!f) { perror(path); exit(2); }
+  fseek(f, 0, SEEK_END);
+  *n = ftell(f);
+  rewind(f);
+  char* buf = (char*)malloc(*n + 1);
+  if (fread(buf, 1, *n, f) != (size_t)*n) { perror(path); exit(2); }
+  fclose(f);
+  return buf;
+}
+
+// usage: capi_asan [scratch directory [the committed table]]; the table defaults
+// to profiles/tune_r6.txt of the tree this program was built in
+// (art-sbir_amd/build_asan/capi_asan -> ../../profiles)
 int main(int argc, char** argv) {
   const char* dir = argc > 1 ? argv[1] : "/tmp";
-  char path[4096];
+  char table[4096], path[4096];
+  if (argc > 2) {
+    snprintf(table, sizeof(table), "%s", argv[2]);
+  } else {
+    const char* slash = strrchr(argv[0], '/');
+    snprintf(table, sizeof(table), "%.*s../../profiles/tune_r6.txt", slash ? (int)(slash - argv[0] + 1) : 0, argv[0]);
+  }
   EXPECT(artsbir_version() == 1);
+
+  // round trip of the committed table through the (still empty) tables: every
+  // entry is stored, and the writer reproduces the file byte for byte (it is in
+  // key order, without duplicates or retired choices)
+  EXPECT(artsbir_tune_load(table) == 143);
+  snprintf(path, sizeof(path), "%s/asan_tune_roundtrip.txt", dir);
+  EXPECT(artsbir_tune_save(path) == 0);
+  {
+    long n0 = 0, n1 = 0;
+    char* want = read_file(table, &n0);
+    char* got = read_file(path, &n1);
+    EXPECT(n0 == n1 && memcmp(want, got, n0) == 0);
+    free(want);
+    free(got);
+  }
 
   // the error buffer: a path far longer than the 512-byte message buffer
   char longpath[3000];
