@@ -18,12 +18,28 @@ sequenced explicitly over the C-ABI kernels:
     GEMM runs once over G x B images, while BatchNorm statistics, running
     statistics and the BN backward stay per segment — the same arithmetic as G
     separate calls;
+  * a Bottleneck followed by another one leaves its tail (bn3 + residual add +
+    ReLU) to the next block's conv1 forward (artsbir_block_out_conv1x1_fwd, bf16
+    training): one pass writes the block output and feeds it to conv1;
   * the BatchNorm backward reduction (sum g, sum g*xhat) of a BN whose output
     gradient comes out of a data-gradient GEMM is fused into that GEMM's
-    epilogue (artsbir_conv2d_dgrad_bnb), which stores g = d * relu-mask;
+    epilogue (artsbir_conv2d_dgrad_bnb), which stores g = d * relu-mask; the
+    deterministic mode reduces in a fixed order in a pass of its own instead;
+  * the block-output BatchNorm backward (bn3 and the downsample BN) is folded
+    through the 1x1 convs before it (artsbir_conv1x1_dgrad_fold): their data and
+    weight gradients are computed from g and the conv input, with the column
+    sums of that input from the forward, so no dy3 / dyd tensor and no apply
+    pass exist; in layer 1 the same kernel also accumulates the weight-gradient
+    operands (artsbir_conv1x1_dgrad_fold_wg);
+  * weight gradients run on a side stream beside the main stream's
+    data-gradient / BatchNorm chain (_on_side), joined at the end of the backward;
   * weights are re-packed from the f32 parameters (reference layout, so
     state_dicts interchange) into the kernel layouts whenever a parameter
     changes (torch version counter or an optimizer step of optim.Adam here).
+
+The backward of one Bottleneck reads top to bottom in _block_bwd; the step
+"backward of a conv, then of the BatchNorm its input came out of" is
+_conv_bn_bwd, for the blocks and the stem alike.
 
 No op of this module runs on the CPU or through a PyTorch kernel except
 allocation (torch.empty / torch.zeros) — the product path fails if the
@@ -31,6 +47,7 @@ native library is missing.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from dataclasses import dataclass
@@ -87,8 +104,12 @@ FUSE_BLOCK_CONV1 = [True]
 
 
 def set_deterministic(on: bool = True) -> bool:
-    """switch the deterministic mode (fixed-order f64 BatchNorm reductions, forward
-    and backward; unfused data gradients); returns the old value"""
+    """switch the deterministic mode: fixed-order f64 BatchNorm reductions, in the
+    forward from the stored conv output (so no block tail is left to the next
+    conv1), in the backward by a reduce pass of its own instead of the
+    data-gradient epilogues' atomics.  The block-output BatchNorm backward is
+    folded through the 1x1 convs in this mode too, fed by that reduce pass
+    (_bn_reduce_g).  Returns the old value"""
     global DETERMINISTIC
     old, DETERMINISTIC = DETERMINISTIC, bool(on)
     _hip.lib().artsbir_set_deterministic(1 if DETERMINISTIC else 0)
@@ -161,6 +182,33 @@ def _s():
 def _at(t, i):
     """raw pointer of image i of an NHWC tensor (None -> NULL)"""
     return None if t is None else t[i].data_ptr()
+
+
+def _out_hw(H, W, R, S, stride, pad):
+    """output height and width of a convolution"""
+    return (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1
+
+
+# algorithmic element counts of the nbytes= declarations (bench.py's roofline)
+def _res_elems(n, res_mode):
+    """elements read of the residual added to a data gradient of n elements
+    (res_mode 1: as is; 2: before its 2x2 AvgPool, a quarter of them)"""
+    return n if res_mode == 1 else n // 4 if res_mode == 2 else 0
+
+
+def _fused_bn_elems(n, fused):
+    """elements read by a BN-backward reduction fused into a data gradient of n
+    elements: y of every target and the ReLU mask (kind 0: the block output;
+    kind 3: its bit mask)"""
+    if fused is None:
+        return 0
+    return n * (fused[0].ntarget + {0: 1.0, 3: 1.0 / 16}.get(fused[0].kind, 0.0))
+
+
+def _fold_elems(px, co, ci, G, fused):
+    """operand elements of the folded 1x1 data gradient: g, x, the per-segment
+    weights, dx, and bn2's y when its reduction is fused in"""
+    return px * co + px * ci + G * ci * (co + ci) + px * ci + (px * ci if fused is not None else 0)
 
 
 @dataclass
@@ -383,22 +431,14 @@ class Engine:
     def _side_gemm_tn(self, M, N, K, dy, ldd, x, ldx, dw):
         """_gemm_tn of a weight gradient on the side stream (as _wgrad), its
         operands held until the backward's stream join"""
-        if not OVERLAP_WGRAD or SKIP_WGRAD[0]:
-            if not SKIP_WGRAD[0]:
-                self._gemm_tn(M, N, K, dy, ldd, x, ldx, dw)
+        if SKIP_WGRAD[0]:
             return
-        main = torch.cuda.current_stream()
-        side = self._side_stream(dy.device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
+        with self._on_side(dy.device, dy, x):
             self._gemm_tn(M, N, K, dy, ldd, x, ldx, dw)
-        self._side_keep.append(dy)
-        self._side_keep.append(x)
 
     def _conv(self, a: Act, fw, cout, R, S, stride, pad, stats_buf=None):
         B, H, W, C = a.shape
-        Ho = (H + 2 * pad - R) // stride + 1
-        Wo = (W + 2 * pad - S) // stride + 1
+        Ho, Wo = _out_hw(H, W, R, S, stride, pad)
         y = self._empty(B, Ho, Wo, cout, device=a.t.device)
         d = self._desc(B, H, W, C, cout, R, S, stride, pad)
         bn = a.bn
@@ -442,11 +482,15 @@ class Engine:
         B, Ho, Wo, _ = y.shape
         return y, self._bn(bnmod, sb, (B // self._G) * Ho * Wo, train)
 
-    def _act_pool(self, x, bn, relu, pool, colsum=False):
+    def _act_pool(self, x, bn, relu, pool):
         """relu(bn(x)) (+ 2x2 avgpool), one launch for all G segments (segment s
-        normalised with its own BN block).  colsum: also return the output's column
+        normalised with its own BN block)"""
+        return self._act_pool_cs(x, bn, relu, pool, False)[0]
+
+    def _act_pool_cs(self, x, bn, relu, pool, colsum):
+        """_act_pool returning (out, cs).  colsum: cs holds the output's column
         sums per segment, [G][NSLOT][C] replica rows (the folded BN backward's
-        1^T x of the conv that reads it)"""
+        1^T x of the conv that reads it); else None"""
         B, H, W, C = x.shape
         p = max(pool, 1)
         out = self._empty(B, H // p, W // p, C, device=x.device)
@@ -456,7 +500,7 @@ class Engine:
              W, C, G, ptr(out), ptr(cs), _s(), kernel="act_pool_kernel",
              nbytes=float(x.element_size() * B * C * (H * W + (H // p) * (W // p))),
              tag=f"act_pool {B}x{H}x{W}x{C} pool{pool}")
-        return (out, cs) if colsum else out
+        return out, cs
 
     # ------------------------------------------------ inference (folded BN)
     def bn_stats_changed(self):
@@ -502,8 +546,7 @@ class Engine:
         fw, bias = fb
         cout, _, R, S = conv.weight.shape
         B, H, W, C = x.shape
-        Ho = (H + 2 * pad - R) // stride + 1
-        Wo = (W + 2 * pad - S) // stride + 1
+        Ho, Wo = _out_hw(H, W, R, S, stride, pad)
         y = self._empty(B, Ho, Wo, cout, device=x.device)
         d = self._desc(B, H, W, C, cout, R, S, stride, pad)
         es = y.element_size()
@@ -519,14 +562,7 @@ class Engine:
         m = self.model
         ev = self._eval_packed()
         pk = self.packed()
-        G = len(xs)
-        Bs, cin, R, R2 = xs[0].shape
-        B = G * Bs
-        dev = xs[0].device
-        x0 = self._empty(B, R, R2, 8, device=dev)
-        for i, xi in enumerate(xs):
-            xi = xi.contiguous().float()
-            call("artsbir_pack_input", self.dt, ptr(xi), Bs, cin, R, R2, _at(x0, i * Bs), _s())
+        x0 = self._pack_input(xs)
         # the stem's few-channel convs stay on their direct kernels (sconv / hconv,
         # no bias epilogue) with the eval BN applied by act_pool: faster than the
         # GEMM kernel with a fused epilogue at 8 / 32 input channels
@@ -552,6 +588,16 @@ class Engine:
         return out
 
     # ---------------------------------------------------------------- forward
+    def _pack_input(self, xs):
+        """the G NCHW f32 input batches as one NHWC tensor of the compute dtype,
+        channels padded to 8 (segment after segment)"""
+        Bs, cin, R, R2 = xs[0].shape
+        x0 = self._empty(len(xs) * Bs, R, R2, 8, device=xs[0].device)
+        for i, xi in enumerate(xs):
+            xi = xi.contiguous().float()
+            call("artsbir_pack_input", self.dt, ptr(xi), Bs, cin, R, R2, _at(x0, i * Bs), _s())
+        return x0
+
     def forward(self, x, train: bool, save: bool):
         """x: [B,3,R,R] or a list of G such batches (G separate reference forward
         calls run as one batch of G BN segments).  Returns ([G*B, out], ctx)."""
@@ -568,18 +614,11 @@ class Engine:
             return self._forward_eval(xs), None
         m = self.model
         pk = self.packed()
-        Bs, cin, R, R2 = xs[0].shape
-        B = G * Bs
-        dev = xs[0].device
-        nstat = 2 * NSLOT * m.total_bn_channels() * G if train else 0
-        stats = _Arena(torch.zeros(max(nstat, 1), dtype=torch.float32, device=dev), NSLOT * 2)
-        ctx = {"train": train, "B": B, "G": G}
+        stats = _Arena.zeros(m.total_bn_channels() * G if train else 0, xs[0].device)
+        ctx = {"train": train, "B": G * xs[0].shape[0], "G": G}
 
         # stem (models.py:345-350)
-        x0 = self._empty(B, R, R2, 8, device=dev)
-        for i, xi in enumerate(xs):
-            xi = xi.contiguous().float()
-            call("artsbir_pack_input", self.dt, ptr(xi), Bs, cin, R, R2, _at(x0, i * Bs), _s())
+        x0 = self._pack_input(xs)
         (fw1, _), (fw2, _), (fw3, _) = pk["stem"]
         y1, b1 = self._conv_bn(Act(x0), m.conv1, m.bn1, fw1, 2, 1, train, stats)
         a1 = self._act_pool(y1, b1, 1, 0)
@@ -587,11 +626,8 @@ class Engine:
         a2 = self._act_pool(y2, b2, 1, 0)
         y3, b3 = self._conv_bn(Act(a2), m.conv3, m.bn3, fw3, 1, 1, train, stats)
         fold = train and save and self._fold_on()
-        h_cs = None
-        if fold:  # the stem output is the first block's downsample input: its column sums for the fold
-            h, h_cs = self._act_pool(y3, b3, 1, 2, colsum=True)
-        else:
-            h = self._act_pool(y3, b3, 1, 2)
+        # the stem output is the first block's downsample input: its column sums for the fold
+        h, h_cs = self._act_pool_cs(y3, b3, 1, 2, fold)
         if save:
             ctx["stem"] = dict(x0=x0, y1=y1, a1=a1, y2=y2, a2=a2, y3=y3, b1=b1, b2=b2, b3=b3)
 
@@ -670,24 +706,16 @@ class Engine:
         s = blk.stride
         a1 = self._act_pool(y1, b1, 1, 0)
         y2, b2 = self._conv_bn(Act(a1), blk.conv2, blk.bn2, bp["conv2"][0], 1, 1, train, stats)
-        cs2 = csd = None
-        if fold:  # conv3's input with its column sums (the folded BN backward's 1^T x)
-            p2, cs2 = self._act_pool(y2, b2, 1, s if s > 1 else 0, colsum=True)
-        else:
-            p2 = self._act_pool(y2, b2, 1, s if s > 1 else 0)
-        c3in = Act(p2)
-        y3, b3 = self._conv_bn(c3in, blk.conv3, blk.bn3, bp["conv3"][0], 1, 0, train, stats)
-        yd = bd = pd = None
+        # conv3's input, under the fold with its column sums (the folded BN backward's 1^T x)
+        p2, cs2 = self._act_pool_cs(y2, b2, 1, s if s > 1 else 0, fold)
+        y3, b3 = self._conv_bn(Act(p2), blk.conv3, blk.bn3, bp["conv3"][0], 1, 0, train, stats)
+        yd = bd = pd = csd = None
         if blk.downsample is not None:
             if s > 1:
-                if fold:
-                    pd, csd = self._act_pool(h, None, 0, s, colsum=True)
-                else:
-                    pd = self._act_pool(h, None, 0, s)
-                din = pd
+                din, csd = self._act_pool_cs(h, None, 0, s, fold)
+                pd = din
             else:
-                din = h
-                csd = h_cs
+                din, csd = h, h_cs
             yd, bd = self._conv_bn(Act(din), blk.downsample[1], blk.downsample[2], bp["down"][0], 1, 0, train, stats)
         ctx = dict(h=h, y1=y1, a1=a1, y2=y2, p2=p2, y3=y3, yd=yd, pd=pd, out=None, bits=None, b1=b1, b2=b2, b3=b3,
                    bd=bd, cs2=cs2, csd=csd, h_cs=h_cs)
@@ -755,8 +783,7 @@ class Engine:
         _hip.lib().artsbir_set_deterministic(1 if DETERMINISTIC else 0)
         dev = dout.device
         grads = self.grad_buffer(dev)
-        ws = _Arena(torch.zeros(max(2 * NSLOT * m.total_bn_channels() * 2 * G, 1), dtype=torch.float32, device=dev),
-                    NSLOT * 2)
+        ws = _Arena.zeros(m.total_bn_channels() * 2 * G, dev)
         # the hook only sees a backward that carries every branch of the step
         # (one batched multi-branch pass); per-branch backwards accumulate and
         # are reduced after the last one by the hook's finish()
@@ -779,9 +806,7 @@ class Engine:
         self._stem_bwd(m, pk, ctx["stem"], dh, grads, ws)
         if hook is not None:
             hook.end(streams)  # block 0, the stem and anything unreported
-        if OVERLAP_WGRAD:
-            torch.cuda.current_stream().wait_stream(self._side_stream(dev))
-        self._side_keep = []
+        self._join_side(dev)
         return grads
 
     def _attnpool_bwd(self, ap, pk, c, dout, grads):
@@ -837,53 +862,79 @@ class Engine:
             call("artsbir_tokens_bwd_ex", self.dt, ptr(dtok), ptr(d0), B, P, C, ptr(dh), _s())
         return dh
 
-    def _seg_desc(self, kind, pool, targets, Bs, H, W, C):
-        """a BN-backward descriptor covering all G segments in one launch
-        (tensors advance by Bs images per segment, parameters by one block)"""
+    @staticmethod
+    def _out_bn(blk, c):
+        """the BatchNorms producing a Bottleneck's output, bn3 and the downsample's
+        if there is one: BN-backward targets [(y, BNState)] and their modules"""
+        if blk.downsample is None:
+            return [(c["y3"], c["b3"])], [blk.bn3]
+        return [(c["y3"], c["b3"]), (c["yd"], c["bd"])], [blk.bn3, blk.downsample[2]]
+
+    def _bnb_desc(self, kind, pool, targets, mask, mask_bn, slots, nseg):
+        """the BN-backward descriptor of targets [(y, BNState)] (slots: their
+        [G][NSLOT][2][C] reduction slots, or None for an apply pass that only
+        reads coefficients).  nseg = G: the reduce / apply passes' form, one
+        launch over all G segments (tensors advance by B / G images per segment,
+        parameters, coefficients and slots by the strides).  nseg = 0: the form a
+        data-gradient GEMM takes for its epilogue, the whole batch B — the GEMM
+        call itself carries G and the parameter stride.  The pass fills in d,
+        gout, coef and dy."""
+        B, H, W, C = targets[0][0].shape
         desc = _hip.BnBwdDesc()
-        desc.dtype = self.dt
-        desc.kind = kind
-        desc.pool = pool
-        desc.ntarget = len(targets)
+        desc.dtype, desc.kind, desc.pool, desc.ntarget = self.dt, kind, pool, len(targets)
+        desc.mask = ptr(mask)
+        desc.mask_bn = ptr(mask_bn.block) if mask_bn is not None else None
         for i, (y, st) in enumerate(targets):
-            desc.y[i] = ptr(y)
-            desc.mean[i] = ptr(st.mean)
-            desc.istd[i] = ptr(st.istd)
-        desc.B, desc.H, desc.W, desc.C = Bs, H, W, C
-        desc.nseg = self._G
-        desc.pstride, desc.cstride, desc.sstride = 4 * C, 3 * C, 2 * NSLOT * C
+            desc.y[i], desc.mean[i], desc.istd[i] = ptr(y), ptr(st.mean), ptr(st.istd)
+            if slots is not None:
+                desc.slots[i] = ptr(slots[i])
+        desc.B, desc.H, desc.W, desc.C = B // nseg if nseg else B, H, W, C
+        if nseg:
+            desc.nseg = nseg
+            desc.pstride, desc.cstride, desc.sstride = 4 * C, 3 * C, 2 * NSLOT * C
         return desc
+
+    def _bn_slots(self, targets, ws):
+        """zeroed reduction slots [G][NSLOT][2][C] per target"""
+        return [ws.take(y.shape[-1] * self._G) for y, _ in targets]
+
+    def _bn_reduce(self, desc, d, targets, g=None):
+        """the reduce pass of desc over the gradient d: Σd', Σd'·x̂ of every target
+        and segment into the slots (d' = d * relu mask); g: d' is stored there"""
+        y0 = targets[0][0]
+        B, H, W, C = y0.shape
+        kind, nt = desc.kind, len(targets)
+        desc.d, desc.gout = ptr(d), ptr(g)
+        call("artsbir_bn_bwd_reduce", desc, _s(), kernel=f"bn_bwd_reduce_kernel<{kind}>",
+             nbytes=float(y0.element_size() * B * H * W * C * (1.0 / max(desc.pool, 1) ** 2 + nt + (kind == 0)
+                                                                 + (g is not None))),
+             tag=f"bn_bwd_reduce k{kind} {B}x{H}x{W}x{C} t{nt}{' +g' if g is not None else ''}")
+
+    def _bn_apply(self, desc, d, targets, bnmods, slots, grads, gout=None):
+        """one finalisation per target for all segments (parameter gradients,
+        coefficients), then the apply pass of desc over d: returns dy per target;
+        gout: d * relu mask is stored there (kind 0)"""
+        y0 = targets[0][0]
+        B, H, W, C = y0.shape
+        kind, nt = desc.kind, len(targets)
+        dys = [torch.empty_like(y) for y, _ in targets]
+        coefs = self._bn_coefs(targets, bnmods, slots, grads)
+        for i in range(nt):
+            desc.coef[i], desc.dy[i] = ptr(coefs[i]), ptr(dys[i])
+        desc.d, desc.gout = ptr(d), ptr(gout)
+        call("artsbir_bn_bwd_apply", desc, _s(), kernel=f"bn_bwd_apply_kernel<{kind}>",
+             nbytes=float(y0.element_size() * B * H * W * C * (1.0 / max(desc.pool, 1) ** 2 + 2 * nt
+                                                                 + (gout is not None))),
+             tag=f"bn_bwd_apply k{kind} {B}x{H}x{W}x{C} t{nt}")
+        return dys
 
     def _bn_bwd(self, kind, d, targets, bnmods, ws, grads, mask=None, mask_bn=None, pool=0, gout=None):
         """BatchNorm backward as a reduce pass + apply pass, each one launch over
         all G segments.  targets: list of (y, BNState); returns list of dy tensors"""
-        y0 = targets[0][0]
-        B, H, W, C = y0.shape
-        G = self._G
-        Bs = B // G
-        dys = [torch.empty_like(y) for y, _ in targets]
-        slots = [ws.take(C * G) for _ in targets]  # [G][NSLOT][2][C] per target
-        desc = self._seg_desc(kind, pool, targets, Bs, H, W, C)
-        desc.d = ptr(d)
-        desc.mask = ptr(mask)
-        desc.mask_bn = ptr(mask_bn.block) if mask_bn is not None else None
-        for i in range(len(targets)):
-            desc.slots[i] = ptr(slots[i])
-        call("artsbir_bn_bwd_reduce", desc, _s(), kernel=f"bn_bwd_reduce_kernel<{kind}>",
-             nbytes=float(y0.element_size() * B * H * W * C * (1.0 / max(pool, 1) ** 2 + len(targets)
-                                                                 + (1 if kind == 0 else 0))),
-             tag=f"bn_bwd_reduce k{kind} {B}x{H}x{W}x{C} t{len(targets)}")
-        # one finalisation per target for all segments, then the apply
-        coefs = self._bn_coefs(targets, bnmods, slots, grads, float(Bs * H * W))
-        for i in range(len(targets)):
-            desc.coef[i] = ptr(coefs[i])
-            desc.dy[i] = ptr(dys[i])
-        desc.gout = ptr(gout)
-        call("artsbir_bn_bwd_apply", desc, _s(), kernel=f"bn_bwd_apply_kernel<{kind}>",
-             nbytes=float(y0.element_size() * B * H * W * C * (1.0 / max(pool, 1) ** 2 + 2 * len(targets)
-                                                                 + (1 if gout is not None else 0))),
-             tag=f"bn_bwd_apply k{kind} {B}x{H}x{W}x{C} t{len(targets)}")
-        return dys
+        slots = self._bn_slots(targets, ws)
+        desc = self._bnb_desc(kind, pool, targets, mask, mask_bn, slots, self._G)
+        self._bn_reduce(desc, d, targets)
+        return self._bn_apply(desc, d, targets, bnmods, slots, grads, gout)
 
     def _bn_reduce_g(self, d, targets, ws, mask=None, kind=0, mask_bn=None):
         """the reduce half of _bn_bwd: g = d * relu mask is written (kind 0: the
@@ -892,29 +943,18 @@ class Engine:
         deterministic mode), no apply pass — the BN backward is then folded
         through the 1x1 convs.  Returns (g, fused) in the form of a fused data
         gradient's hand-over (_bnb_fused_desc)."""
-        y0 = targets[0][0]
-        B, H, W, C = y0.shape
-        G = self._G
         g = torch.empty_like(d)
-        slots = [ws.take(C * G) for _ in targets]
-        desc = self._seg_desc(kind, 0, targets, B // G, H, W, C)
-        desc.d = ptr(d)
-        desc.mask = ptr(mask)
-        desc.mask_bn = ptr(mask_bn.block) if mask_bn is not None else None
-        desc.gout = ptr(g)
-        for i in range(len(targets)):
-            desc.slots[i] = ptr(slots[i])
-        call("artsbir_bn_bwd_reduce", desc, _s(), kernel=f"bn_bwd_reduce_kernel<{kind}>",
-             nbytes=float(y0.element_size() * B * H * W * C * (2 + (kind == 0) + len(targets))),
-             tag=f"bn_bwd_reduce k{kind} {B}x{H}x{W}x{C} t{len(targets)} +g")
+        slots = self._bn_slots(targets, ws)
+        self._bn_reduce(self._bnb_desc(kind, 0, targets, mask, mask_bn, slots, self._G), d, targets, g)
         return g, (None, slots, targets)
 
-    def _bn_coefs(self, targets, bnmods, slots, grads, count):
+    def _bn_coefs(self, targets, bnmods, slots, grads):
         """parameter gradients (+=) and apply coefficients [G][3][C] of every
         segment, one launch per BN target"""
         coefs = []
         for i, ((y, st), bnm) in enumerate(zip(targets, bnmods)):
-            C = y.shape[-1]
+            B, H, W, C = y.shape
+            count = float(B // self._G * H * W)  # elements per channel and segment
             coef = torch.empty(self._G, 3, C, dtype=torch.float32, device=y.device)
             call("artsbir_bn_bwd_finalize_seg", ptr(slots[i]), self._G, 2 * NSLOT * C, C, count,
                  ptr(bnm.weight.detach()), ptr(st.buf[0, 1]), 4 * C, ptr(grads[bnm.weight]), ptr(grads[bnm.bias]),
@@ -925,45 +965,47 @@ class Engine:
     def _bnb_fused_desc(self, kind, targets, ws, mask=None, mask_bn=None):
         """descriptor of a BN-backward reduction fused into the data-gradient GEMM
         that produces its input gradient (all G segments; slots [G][NSLOT][2][C])"""
-        y0 = targets[0][0]
-        B, H, W, C = y0.shape
-        desc = _hip.BnBwdDesc()
-        desc.dtype = self.dt
-        desc.kind = kind
-        desc.pool = 0
-        desc.mask = ptr(mask)
-        desc.mask_bn = ptr(mask_bn.block) if mask_bn is not None else None
-        desc.ntarget = len(targets)
-        slots = []
-        for i, (y, st) in enumerate(targets):
-            desc.y[i] = ptr(y)
-            desc.mean[i] = ptr(st.mean)
-            desc.istd[i] = ptr(st.istd)
-            sl = ws.take(C * self._G)
-            slots.append(sl)
-            desc.slots[i] = ptr(sl)
-        desc.B, desc.H, desc.W, desc.C = B, H, W, C
-        return desc, slots, targets
+        slots = self._bn_slots(targets, ws)
+        return self._bnb_desc(kind, 0, targets, mask, mask_bn, slots, 0), slots, targets
 
     def _bn_finish(self, g, fused, bnmods, grads):
         """apply pass of a fused BN-backward: g (masked) -> dy per target, one
         launch over all G segments"""
         _, slots, targets = fused
-        y0 = targets[0][0]
-        B, H, W, C = y0.shape
-        G = self._G
-        Bs = B // G
-        dys = [torch.empty_like(y) for y, _ in targets]
-        coefs = self._bn_coefs(targets, bnmods, slots, grads, float(Bs * H * W))
-        desc = self._seg_desc(2, 0, targets, Bs, H, W, C)
-        desc.d = ptr(g)
-        for i in range(len(targets)):
-            desc.coef[i] = ptr(coefs[i])
-            desc.dy[i] = ptr(dys[i])
-        call("artsbir_bn_bwd_apply", desc, _s(), kernel="bn_bwd_apply_kernel<2>",
-             nbytes=float(y0.element_size() * B * H * W * C * (1 + 2 * len(targets))),
-             tag=f"bn_bwd_apply k2 {B}x{H}x{W}x{C} t{len(targets)}")
-        return dys
+        desc = self._bnb_desc(2, 0, targets, None, None, None, self._G)
+        return self._bn_apply(desc, g, targets, bnmods, slots, grads)
+
+    # ------------------------------------------------------------- side stream
+    @contextlib.contextmanager
+    def _on_side(self, device, *keep, main=False):
+        """work of the body on the weight-gradient stream, ordered after what the
+        caller's stream has enqueued so far (main, or OVERLAP_WGRAD off: in order
+        on the caller's stream).  keep: the tensors that work reads; yields a list
+        for those the body allocates.
+
+        The caching allocator must not hand these to the main stream before the
+        side stream is done with them: they stay referenced until the backward's
+        final join (_join_side: main waits for side), after which their blocks
+        return to the main stream's pool in stream order.  (record_stream would
+        instead tie every block to the side stream's progress, so the allocator
+        keeps mallocing fresh blocks — ~60 hipMallocs a step, the pool creeping
+        towards the 288 GB capacity, and an occasional seconds-long stall when
+        the driver has to make room.)"""
+        keep = list(keep)
+        if main or not OVERLAP_WGRAD:
+            yield keep
+            return
+        side = self._side_stream(device)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            yield keep
+        self._side_keep.extend(keep)
+
+    def _join_side(self, device):
+        """the caller's stream waits for the side stream's work; its operands are released"""
+        if OVERLAP_WGRAD:
+            torch.cuda.current_stream().wait_stream(self._side_stream(device))
+        self._side_keep = []
 
     def _side_stream(self, device):
         """the weight-gradient stream; with SIDE_CUS > 0 it may only use that many
@@ -988,23 +1030,9 @@ class Engine:
         of the main stream; backward() joins the streams at the end."""
         if SKIP_WGRAD[0]:  # measurement only (tools/cu_mask_sweep.py): the main stream's critical path
             return
-        if not OVERLAP_WGRAD or (WGRAD_MAIN and WGRAD_MAIN == ("1x1" if conv.weight.shape[2] == 1 else "3x3")):
-            return self._wgrad_sync(dy, a, conv, stride, pad, grads, ci_pad)
-        main = torch.cuda.current_stream()
-        side = self._side_stream(dy.device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
+        in_order = bool(WGRAD_MAIN) and WGRAD_MAIN == ("1x1" if conv.weight.shape[2] == 1 else "3x3")
+        with self._on_side(dy.device, dy, a.t, main=in_order):
             self._wgrad_sync(dy, a, conv, stride, pad, grads, ci_pad)
-        # the caching allocator must not hand these to the main stream before
-        # the side stream is done with them: they stay referenced until the
-        # backward's final join (main waits for side), after which their blocks
-        # return to the main stream's pool in stream order.  (record_stream
-        # would instead tie every block to the side stream's progress, so the
-        # allocator keeps mallocing fresh blocks — ~60 hipMallocs a step, the
-        # pool creeping towards the 288 GB capacity, and an occasional
-        # seconds-long stall when the driver has to make room.)
-        self._side_keep.append(dy)
-        self._side_keep.append(a.t)
 
     def _wgrad_sync(self, dy, a: Act, conv, stride, pad, grads, ci_pad=None):
         B, H, W, C = a.shape
@@ -1047,9 +1075,7 @@ class Engine:
         es = dx.element_size()
         px = B * H * W
         # algorithmic bytes: dy, w, dx once; residual; BN-backward operands (y_t, mask)
-        nb = px * co + co * R * S * C + px * C + (px * C if res_mode == 1 else px * C // 4 if res_mode == 2 else 0)
-        if fused is not None:
-            nb += px * C * (fused[0].ntarget + {0: 1.0, 3: 1.0 / 16}.get(fused[0].kind, 0.0))
+        nb = px * co + co * R * S * C + px * C + _res_elems(px * C, res_mode) + _fused_bn_elems(px * C, fused)
         nbytes = float(es * nb)
         if fused is None:
             call("artsbir_conv2d_dgrad", d, ptr(dy), ptr(dw), ptr(dx), ptr(res), res_mode, _s(),
@@ -1089,7 +1115,7 @@ class Engine:
         d = self._desc(B, H, W, ci, co, 1, 1, 1, 0)
         px = B * H * W
         es = dx.element_size()
-        nb = px * co + px * ci + self._G * ci * (co + ci) + px * ci + (px * ci if fused is not None else 0)
+        nb = _fold_elems(px, co, ci, self._G, fused)
         call("artsbir_conv1x1_dgrad_fold", d, ptr(g), ptr(x), ptr(wout), ptr(bias), ptr(dx),
              ctypes.byref(fused[0]) if fused is not None else None, self._G, 4 * ci, _s(), kernel="auto",
              flops=2.0 * px * ci * (co + ci), nbytes=float(es * nb),
@@ -1118,8 +1144,7 @@ class Engine:
         d = self._desc(B, H, W, ci, co, 1, 1, 1, 0)
         px = B * H * W
         es = dx.element_size()
-        nb = es * (px * co + px * ci + G * ci * (co + ci) + px * ci + (px * ci if fused is not None else 0)) \
-            + 4 * G * (co + ci) * ci
+        nb = es * _fold_elems(px, co, ci, G, fused) + 4 * G * (co + ci) * ci
         call("artsbir_conv1x1_dgrad_fold_wg", d, ptr(g), ptr(x), ptr(wout), ptr(bias), ptr(dx),
              ctypes.byref(fused[0]) if fused is not None else None, G, 4 * ci, ptr(P), ptr(gram), _s(),
              kernel="auto", flops=4.0 * px * ci * (co + ci), nbytes=float(nb),
@@ -1136,17 +1161,13 @@ class Engine:
         _dgrad_fold_wg (only the combine runs here)"""
         if SKIP_WGRAD[0]:
             return
-        main = torch.cuda.current_stream()
-        side = self._side_stream(g.device) if OVERLAP_WGRAD else main
-        if side is not main:
-            side.wait_stream(main)
         G = self._G
         B, H, W, ci = x.shape
         co = conv.weight.shape[0]
         Bs = B // G
         Ms = Bs * H * W
         es = x.element_size()
-        with torch.cuda.stream(side):
+        with self._on_side(g.device, g, x, coef, st.buf) as keep:
             # [P | Gram | colsums] of every segment in one zeroed buffer, then the
             # combine's workspace (W in f32, T = W Gram)
             nP, nG = G * co * ci, G * ci * ci
@@ -1155,7 +1176,6 @@ class Engine:
                 P, gram, buf = pg
                 if own_cs:
                     cs = torch.zeros(G, 1, ci, dtype=torch.float32, device=x.device)
-                    self._side_keep.append(cs)
             else:
                 buf = torch.zeros(nP + nG + (G * ci if own_cs else 0), dtype=torch.float32, device=x.device)
                 P, gram = buf[:nP].view(G, co, ci), buf[nP:nP + nG].view(G, ci, ci)
@@ -1176,8 +1196,7 @@ class Engine:
                  ptr(coef), ptr(st.buf), 4 * co, ptr(grads[conv.weight]), ptr(wsp), _s(), kernel="fold_combine",
                  flops=2.0 * G * co * ci * ci, nbytes=float(4 * (G * (co * ci + ci * ci) + 3 * co * ci)),
                  tag=f"fold_combine {co}x{ci}")
-        if side is not main:
-            self._side_keep.extend([g, x, coef, st.buf, buf, wsp, cs])
+            keep.extend([buf, wsp, cs])
 
     # ------------------------- bn1 folded through conv1 with its own input (y-side)
     def _fold_weights_y(self, packs, conv, coef, st: BNState):
@@ -1206,10 +1225,8 @@ class Engine:
         d = self._desc(B, H, W, ci, co, 1, 1, 1, 0)
         px = B * H * W
         es = dx.element_size()
-        nb = 2 * px * co + self._G * ci * 2 * co + px * ci + (px * ci if res_mode == 1 else
-                                                                px * ci // 4 if res_mode == 2 else 0)
-        if fused is not None:
-            nb += px * ci * (fused[0].ntarget + {0: 1.0, 3: 1.0 / 16}.get(fused[0].kind, 0.0))
+        nb = (2 * px * co + self._G * ci * 2 * co + px * ci + _res_elems(px * ci, res_mode)
+              + _fused_bn_elems(px * ci, fused))
         call("artsbir_conv1x1_dgrad_fold_y", d, ptr(g), ptr(y), ptr(wout), ptr(bias), ptr(dx), ptr(res), res_mode,
              ctypes.byref(fused[0]) if fused is not None else None, self._G, 4 * ci, _s(), kernel="auto",
              flops=2.0 * px * ci * 2 * co, nbytes=float(es * nb),
@@ -1225,17 +1242,13 @@ class Engine:
         artsbir_bn_fold_wgrad_combine_y into the gradient buffer"""
         if SKIP_WGRAD[0]:
             return
-        main = torch.cuda.current_stream()
-        side = self._side_stream(g.device) if OVERLAP_WGRAD else main
-        if side is not main:
-            side.wait_stream(main)
         G = self._G
         B, H, W, ci = x.shape
         co = conv.weight.shape[0]
         Bs = B // G
         Ms = Bs * H * W
         es = x.element_size()
-        with torch.cuda.stream(side):
+        with self._on_side(g.device, g, y, x, coef, st.buf) as keep:
             own_cs = cs is None
             buf = torch.zeros(2 * G * co * ci + (G * ci if own_cs else 0), dtype=torch.float32, device=x.device)
             P, Q = buf[:G * co * ci].view(G, co, ci), buf[G * co * ci:2 * G * co * ci].view(G, co, ci)
@@ -1252,8 +1265,7 @@ class Engine:
             call("artsbir_bn_fold_wgrad_combine_y", co, ci, G, ptr(P), ptr(Q), ptr(cs), cs.shape[1], ptr(coef),
                  ptr(st.buf), 4 * co, ptr(grads[conv.weight]), _s(), kernel="fold_wgrad_combine_kernel",
                  nbytes=float(4 * (2 * G * co * ci + 2 * co * ci)), tag=f"fold_combine_y {co}x{ci}")
-        if side is not main:
-            self._side_keep.extend([g, y, x, coef, st.buf, buf, cs])
+            keep.extend([buf, cs])
 
     def _block_bwd(self, blk, bp, c, dout, grads, ws, fused_res=None, prev=None):
         """backward of one Bottleneck.  dout: gradient of the block output, or —
@@ -1261,147 +1273,138 @@ class Engine:
         reduction already done by the producing data-gradient GEMM.  prev: the
         (Bottleneck, ctx) feeding this block, whose output BN reduction is fused
         into this block's last data gradient.  Returns (dh, fused for prev)."""
-        h, y1, y2, p2, y3, yd, pd, out = (c[k] for k in ("h", "y1", "y2", "p2", "y3", "yd", "pd", "out"))
-        b1, b2, b3, bd = c["b1"], c["b2"], c["b3"], c["bd"]
+        # the block-output BN (bn3, the downsample BN): g = dout * relu-mask is the
+        # identity branch's gradient; then either coefs (the BN backward is folded
+        # through conv3 / the downsample conv) or dys (their output gradients)
+        g, dys, coefs = self._out_bn_bwd(blk, c, dout, grads, ws, fused_res)
+        # conv3 and bn2 -> dy2
+        folded = coefs is not None
         s = blk.stride
-        has_ds = blk.downsample is not None
-        bnmods = [blk.bn3] + ([blk.downsample[2]] if has_ds else [])
-        # the block-output BN backward folded through conv3 / the downsample conv
-        # (csrc/fold.hip): no dy3 / dyd tensors, their apply pass and re-reads gone
-        fold = fused_res is not None and FOLD_BN[0]
-        dys = coefs = None
-        if fused_res is None and self._fold_on():
-            # no data gradient reduced this BN for us (the last block; the
-            # deterministic mode): a reduce-only pass, then the same fold
-            targets = [(y3, b3)] + ([(yd, bd)] if has_ds else [])
-            dout, fused_res = self._bn_reduce_g(dout, targets, ws, out)
-            fold = True
-        if fold:
-            _, slots, targets = fused_res
-            B3, H3, W3, _ = y3.shape
-            coefs = self._bn_coefs(targets, bnmods, slots, grads, float(B3 // self._G * H3 * W3))
-            gid = dout
-        elif fused_res is not None:
-            dys = self._bn_finish(dout, fused_res, bnmods, grads)
-            gid = dout  # the identity branch's gradient is g itself
+        dy2 = self._conv_bn_bwd(g if folded else dys[0], c["p2"], bp["conv3"], blk.conv3, 0,
+                                (c["y2"], c["b2"], blk.bn2), ws, grads, pool=s if s > 1 else 0,
+                                fold=(coefs[0], c["b3"], c.get("cs2")) if folded else None)
+        # conv2 and bn1 -> dy1; bn1 folded through conv1 with its input y1
+        # (models.py:198-199): no dy1 but g1 and bn1's coefficients
+        fold1 = folded and self._fold1_on()
+        d1 = self._conv_bn_bwd(dy2, c["a1"], bp["conv2"], blk.conv2, 1, (c["y1"], c["b1"], blk.bn1), ws, grads,
+                               apply=not fold1)
+        # conv1: its weight gradient, the downsample branch beside it, then its data
+        # gradient, which adds that branch and reduces the previous block's output BN
+        w1 = self._conv1_wgrad(blk, bp, c, d1, grads, fold1)
+        res, res_mode = self._down_bwd(blk, bp, c, g, dys, coefs, grads)
+        fprev = self._prev_fused(prev, ws)
+        return self._conv1_dgrad(blk, bp, c, d1, w1, res, res_mode, fprev, fold1), fprev
+
+    def _out_bn_bwd(self, blk, c, dout, grads, ws, fused):
+        """backward of the block-output BatchNorms, as far as it is a pass of its
+        own.  The reduction arrives in one of three ways: fused, done by the next
+        block's data gradient; a reduce-only pass here (the encoder's last block;
+        the deterministic mode); or, without the fold, the full reduce + apply.
+        Returns (g, dys, coefs) — see _block_bwd; g is None where nothing reads it"""
+        targets, bnmods = self._out_bn(blk, c)
+        if fused is None and not self._fold_on():
+            g = None if blk.downsample is not None else torch.empty_like(dout)
+            return g, self._bn_bwd(0, dout, targets, bnmods, ws, grads, mask=c["out"], gout=g), None
+        if fused is None:
+            dout, fused = self._bn_reduce_g(dout, targets, ws, c["out"])
+        if not FOLD_BN[0]:
+            return dout, self._bn_finish(dout, fused, bnmods, grads), None
+        # folded (csrc/fold.hip): no dy3 / dyd tensors, their apply pass and re-reads gone
+        return dout, None, self._bn_coefs(targets, bnmods, fused[1], grads)
+
+    def _conv_bn_bwd(self, dy, x, packs, conv, pad, bn, ws, grads, pool=0, apply=True, fold=None):
+        """backward of a stride-1 conv with input x, then of the BatchNorm + ReLU
+        (+ AvgPool) that x came out of, bn = (y, BNState, module): returns dy of
+        that BatchNorm's input y.  The BN reduction runs in the data gradient's
+        epilogue (_fuse_bnb; not through a pool) or in a pass of its own.
+        fold = (coef, BNState, column sums of x) of the BatchNorm AFTER this 1x1
+        conv: dy is the masked gradient g behind that BatchNorm, which is folded
+        through the conv (_fold_bwd).  apply=False: no apply pass, returns
+        (g, coef) for a caller that folds bn through the conv before it"""
+        y, st, bnmod = bn
+        f = self._bnb_fused_desc(1, [(y, st)], ws, mask_bn=st) if _fuse_bnb() and not pool else None
+        if fold is not None:
+            held = None
+            g = self._fold_bwd(dy, x, packs, conv, *fold, grads, fused=f)
         else:
-            targets = [(y3, b3)] + ([(yd, bd)] if has_ds else [])
-            gid = None if has_ds else torch.empty_like(dout)
-            dys = self._bn_bwd(0, dout, targets, bnmods, ws, grads, mask=out, gout=gid)
-        c3in = Act(p2)
-        c3out = c3in.shape[:3] + (blk.conv3.weight.shape[1],)
-        if fold:
-            fw3 = self._fold_weights(bp["conv3"], blk.conv3, coefs[0], b3)
-            wg3 = self._fold_wg_ok(p2, blk.conv3)
-            wargs = (blk.conv3, bp["conv3"][0], coefs[0], b3, grads, c.get("cs2"))
-            if not wg3:
-                self._wgrad_fold(dout, p2, *wargs)
-            f2 = self._bnb_fused_desc(1, [(y2, b2)], ws, mask_bn=b2) if s == 1 and _fuse_bnb() else None
-            if wg3:
-                g2 = self._dgrad_fold_wg(dout, p2, fw3, *wargs, fused=f2)
-            else:
-                g2 = self._dgrad_fold(dout, p2, fw3, blk.conv3, fused=f2)
-            if f2 is not None:
-                dy2, = self._bn_finish(g2, f2, [blk.bn2], grads)
-            else:
-                dy2, = self._bn_bwd(1, g2, [(y2, b2)], [blk.bn2], ws, grads, mask_bn=b2, pool=s if s > 1 else 0)
-        else:
-            dy3 = dys[0]
-            held = self._wgrad_pre(dy3, c3in, blk.conv3, 1, 0, grads)
-            if s == 1 and _fuse_bnb():
-                f2 = self._bnb_fused_desc(1, [(y2, b2)], ws, mask_bn=b2)
-                g2 = self._dgrad(dy3, bp["conv3"][1], blk.conv3, 0, c3out, fused=f2)
-                self._wgrad_post(held)
-                dy2, = self._bn_finish(g2, f2, [blk.bn2], grads)
-            else:
-                dp = self._dgrad(dy3, bp["conv3"][1], blk.conv3, 0, c3out)
-                self._wgrad_post(held)
-                dy2, = self._bn_bwd(1, dp, [(y2, b2)], [blk.bn2], ws, grads, mask_bn=b2, pool=s if s > 1 else 0)
-        held = self._wgrad_pre(dy2, Act(c["a1"]), blk.conv2, 1, 1, grads)
-        # bn1 folded through conv1 with its input y1 (models.py:198-199): no dy1
-        fold1 = fold and self._fold1_on()
-        held1 = None
-        if fold1:
-            if _fuse_bnb():
-                f1 = self._bnb_fused_desc(1, [(y1, b1)], ws, mask_bn=b1)
-                g1 = self._dgrad(dy2, bp["conv2"][1], blk.conv2, 1, y1.shape, fused=f1)
-            else:  # deterministic: the fixed-order reduce-only pass writes g1
-                da1 = self._dgrad(dy2, bp["conv2"][1], blk.conv2, 1, y1.shape)
-                g1, f1 = self._bn_reduce_g(da1, [(y1, b1)], ws, kind=1, mask_bn=b1)
-            self._wgrad_post(held)
-            B1, H1, W1, _ = y1.shape
-            coef1, = self._bn_coefs([(y1, b1)], [blk.bn1], f1[1], grads, float(B1 // self._G * H1 * W1))
-            fw1 = self._fold_weights_y(bp["conv1"], blk.conv1, coef1, b1)
-            self._wgrad_fold_y(g1, y1, h, blk.conv1, coef1, b1, grads, c.get("h_cs"))
-        elif _fuse_bnb():
-            f1 = self._bnb_fused_desc(1, [(y1, b1)], ws, mask_bn=b1)
-            g1 = self._dgrad(dy2, bp["conv2"][1], blk.conv2, 1, y1.shape, fused=f1)
-            self._wgrad_post(held)
-            dy1, = self._bn_finish(g1, f1, [blk.bn1], grads)
-        else:
-            da1 = self._dgrad(dy2, bp["conv2"][1], blk.conv2, 1, y1.shape)
-            self._wgrad_post(held)
-            dy1, = self._bn_bwd(1, da1, [(y1, b1)], [blk.bn1], ws, grads, mask_bn=b1)
+            held = self._wgrad_pre(dy, Act(x), conv, 1, pad, grads)
+            g = self._dgrad(dy, packs[1], conv, pad, x.shape, fused=f)
+        if not apply and f is None:  # deterministic: the fixed-order reduce-only pass writes g
+            g, f = self._bn_reduce_g(g, [(y, st)], ws, kind=1, mask_bn=st)
+        self._wgrad_post(held)
+        if not apply:
+            return g, self._bn_coefs([(y, st)], [bnmod], f[1], grads)[0]
+        if f is not None:
+            return self._bn_finish(g, f, [bnmod], grads)[0]
+        return self._bn_bwd(1, g, [(y, st)], [bnmod], ws, grads, mask_bn=st, pool=pool)[0]
+
+    def _fold_bwd(self, g, x, packs, conv, coef, st, cs, grads, fused=None):
+        """data and weight gradient of a 1x1 conv with input x through the
+        BatchNorm after it (coef, st; cs: the column sums of x), from the masked
+        gradient g at that BatchNorm's output: returns dx"""
+        fold = self._fold_weights(packs, conv, coef, st)
+        wargs = (conv, packs[0], coef, st, grads, cs)
+        if self._fold_wg_ok(x, conv):
+            return self._dgrad_fold_wg(g, x, fold, *wargs, fused=fused)
+        self._wgrad_fold(g, x, *wargs)
+        return self._dgrad_fold(g, x, fold, conv, fused=fused)
+
+    def _conv1_wgrad(self, blk, bp, c, d1, grads, fold1):
+        """conv1's weight gradient, issued before the downsample branch.  Returns
+        what its data gradient still needs: the held weight gradient (WGRAD_DEFER)
+        or, under FOLD_BN1, the y-side fold weights"""
         if not fold1:
-            held1 = self._wgrad_pre(dy1, Act(h), blk.conv1, 1, 0, grads)
-        if has_ds:
-            din = pd if s > 1 else h
-            dconv = blk.downsample[1]
-            if fold:
-                fwd_ = self._fold_weights(bp["down"], dconv, coefs[1], bd)
-                wargs = (dconv, bp["down"][0], coefs[1], bd, grads, c.get("csd"))
-                if self._fold_wg_ok(din, dconv):
-                    res = self._dgrad_fold_wg(dout, din, fwd_, *wargs)
-                else:
-                    self._wgrad_fold(dout, din, *wargs)
-                    res = self._dgrad_fold(dout, din, fwd_, dconv)
-            else:
-                dyd = dys[1]
-                held = self._wgrad_pre(dyd, Act(din), dconv, 1, 0, grads)
-                res = self._dgrad(dyd, bp["down"][1], dconv, 0, din.shape)
-                self._wgrad_post(held)
-            res_mode = 2 if s > 1 else 1
-        else:
-            res, res_mode = gid, 1
-        fprev = None
-        if prev is not None and _fuse_bnb():
-            pblk, pc = prev
-            ptargets = [(pc["y3"], pc["b3"])] + ([(pc["yd"], pc["bd"])] if pblk.downsample is not None else [])
-            if pc.get("bits") is not None:
-                fprev = self._bnb_fused_desc(3, ptargets, ws, mask=pc["bits"])
-            else:
-                fprev = self._bnb_fused_desc(0, ptargets, ws, mask=pc["out"])
+            return self._wgrad_pre(d1, Act(c["h"]), blk.conv1, 1, 0, grads)
+        g1, coef1 = d1
+        fw1 = self._fold_weights_y(bp["conv1"], blk.conv1, coef1, c["b1"])
+        self._wgrad_fold_y(g1, c["y1"], c["h"], blk.conv1, coef1, c["b1"], grads, c.get("h_cs"))
+        return fw1
+
+    def _conv1_dgrad(self, blk, bp, c, d1, w1, res, res_mode, fprev, fold1):
+        """conv1's data gradient, the block's last launch on the main stream: dh,
+        with the other branch's gradient (res) added and, with fprev, as g of the
+        previous block's output and its BN reduction done"""
         if fold1:
-            dh = self._dgrad_fold_y(g1, y1, fw1, blk.conv1, h.shape, res, res_mode, fused=fprev)
+            return self._dgrad_fold_y(d1[0], c["y1"], w1, blk.conv1, c["h"].shape, res, res_mode, fused=fprev)
+        dh = self._dgrad(d1, bp["conv1"][1], blk.conv1, 0, c["h"].shape, res=res, res_mode=res_mode, fused=fprev)
+        self._wgrad_post(w1)
+        return dh
+
+    def _down_bwd(self, blk, bp, c, g, dys, coefs, grads):
+        """the gradient that reaches the block input beside conv1, as (res,
+        res_mode) of conv1's data-gradient epilogue: the identity's g, or the
+        downsample conv's data gradient (res_mode 2: before its AvgPool)"""
+        if blk.downsample is None:
+            return g, 1
+        s = blk.stride
+        din = c["pd"] if s > 1 else c["h"]
+        dconv = blk.downsample[1]
+        if coefs is not None:
+            res = self._fold_bwd(g, din, bp["down"], dconv, coefs[1], c["bd"], c.get("csd"), grads)
         else:
-            dh = self._dgrad(dy1, bp["conv1"][1], blk.conv1, 0, h.shape, res=res, res_mode=res_mode, fused=fprev)
-            self._wgrad_post(held1)
-        return dh, fprev
+            held = self._wgrad_pre(dys[1], Act(din), dconv, 1, 0, grads)
+            res = self._dgrad(dys[1], bp["down"][1], dconv, 0, din.shape)
+            self._wgrad_post(held)
+        return res, 2 if s > 1 else 1
+
+    def _prev_fused(self, prev, ws):
+        """the hand-over to prev = (Bottleneck, ctx), the block before this one:
+        the descriptor that makes this block's last data gradient reduce prev's
+        output BN (mask: prev's ReLU bits if the forward wrote them, else its output)"""
+        if prev is None or not _fuse_bnb():
+            return None
+        targets, _ = self._out_bn(*prev)
+        bits = prev[1].get("bits")
+        if bits is not None:
+            return self._bnb_fused_desc(3, targets, ws, mask=bits)
+        return self._bnb_fused_desc(0, targets, ws, mask=prev[1]["out"])
 
     def _stem_bwd(self, m, pk, c, dh, grads, ws):
         x0, y1, y2, y3, b1, b2, b3 = (c[k] for k in ("x0", "y1", "y2", "y3", "b1", "b2", "b3"))
-        (_, _), (_, dw2), (_, dw3) = pk["stem"]
+        _, pk2, pk3 = pk["stem"]
         dy3, = self._bn_bwd(1, dh, [(y3, b3)], [m.bn3], ws, grads, mask_bn=b3, pool=2)
-        held = self._wgrad_pre(dy3, Act(c["a2"]), m.conv3, 1, 1, grads)
-        if _fuse_bnb():
-            f2 = self._bnb_fused_desc(1, [(y2, b2)], ws, mask_bn=b2)
-            g2 = self._dgrad(dy3, dw3, m.conv3, 1, y2.shape, fused=f2)
-            self._wgrad_post(held)
-            dy2, = self._bn_finish(g2, f2, [m.bn2], grads)
-        else:
-            da2 = self._dgrad(dy3, dw3, m.conv3, 1, y2.shape)
-            self._wgrad_post(held)
-            dy2, = self._bn_bwd(1, da2, [(y2, b2)], [m.bn2], ws, grads, mask_bn=b2)
-        held = self._wgrad_pre(dy2, Act(c["a1"]), m.conv2, 1, 1, grads)
-        if _fuse_bnb():
-            f1 = self._bnb_fused_desc(1, [(y1, b1)], ws, mask_bn=b1)
-            g1 = self._dgrad(dy2, dw2, m.conv2, 1, y1.shape, fused=f1)
-            self._wgrad_post(held)
-            dy1, = self._bn_finish(g1, f1, [m.bn1], grads)
-        else:
-            da1 = self._dgrad(dy2, dw2, m.conv2, 1, y1.shape)
-            self._wgrad_post(held)
-            dy1, = self._bn_bwd(1, da1, [(y1, b1)], [m.bn1], ws, grads, mask_bn=b1)
+        dy2 = self._conv_bn_bwd(dy3, c["a2"], pk3, m.conv3, 1, (y2, b2, m.bn2), ws, grads)
+        dy1 = self._conv_bn_bwd(dy2, c["a1"], pk2, m.conv2, 1, (y1, b1, m.bn1), ws, grads)
         # the stem conv (models.py:310) has no data gradient, so the main stream
         # has nothing left to do: its weight gradient runs there, beside the side
         # stream's last ones, instead of queued behind them while main idles
@@ -1417,6 +1420,11 @@ class _Arena:
 
     def __init__(self, buf, per_channel):
         self.buf, self.per, self.off = buf, per_channel, 0
+
+    @classmethod
+    def zeros(cls, channels, device):
+        """an arena of BatchNorm slot blocks, [NSLOT][2] f32 per channel"""
+        return cls(torch.zeros(max(2 * NSLOT * channels, 1), dtype=torch.float32, device=device), NSLOT * 2)
 
     def take(self, C):
         n = self.per * C
@@ -1468,7 +1476,7 @@ class ModuleEngine(Engine):
         h = x.detach().permute(0, 2, 3, 1).contiguous().to(self.dtype)
         if hasattr(m, "conv3"):
             nbn = sum(b.num_features for b in m.modules() if isinstance(b, torch.nn.BatchNorm2d))
-            stats = _Arena(torch.zeros(max(2 * NSLOT * nbn, 1), dtype=torch.float32, device=x.device), NSLOT * 2)
+            stats = _Arena.zeros(nbn, x.device)
             out, c, _, _ = self._block_fwd(m, pk, h, train, stats)
             return out.permute(0, 3, 1, 2).float().contiguous(), {"train": train, "c": c}
         out, c = self._attnpool_fwd(m, pk, h)
@@ -1484,14 +1492,12 @@ class ModuleEngine(Engine):
         grads = self.grad_buffer(dev)
         if hasattr(m, "conv3"):
             nbn = sum(b.num_features for b in m.modules() if isinstance(b, torch.nn.BatchNorm2d))
-            ws = _Arena(torch.zeros(max(2 * NSLOT * nbn * 2, 1), dtype=torch.float32, device=dev), NSLOT * 2)
+            ws = _Arena.zeros(nbn * 2, dev)
             d = dout.permute(0, 2, 3, 1).contiguous().to(self.dtype)
             dh, _ = self._block_bwd(m, pk, state["c"], d, grads, ws, None, None)
         else:
             dh = self._attnpool_bwd(m, pk, state["c"], dout.contiguous().float(), grads)
-        if OVERLAP_WGRAD:
-            torch.cuda.current_stream().wait_stream(self._side_stream(dev))
-        self._side_keep = []
+        self._join_side(dev)
         return dh.permute(0, 3, 1, 2).float().contiguous()
 
 
