@@ -1201,7 +1201,7 @@ extern "C" int artsbir_bn_stats_det(int dtype, const void* y, int nseg, long lon
 
 extern "C" int artsbir_act_pool_colsum(int dtype, const void* x, const float* bn, int relu, int pool, int B, int H,
                                        int W, int C, int nseg, void* out, float* colsum, void* stream) {
-  if (C % 8) { set_error("act_pool: C %% 8 != 0"); return -1; }
+  if (C < 8 || C % 8) { set_error("act_pool: C %% 8 != 0"); return -1; }
   if (nseg < 1 || B % nseg) { set_error("act_pool: %d segments do not split %d images", nseg, B); return -1; }
   if (pool > 1 && (H % pool || W % pool)) { set_error("act_pool: H,W not divisible by pool"); return -1; }
   const int Ho = pool > 1 ? H / pool : H, Wo = pool > 1 ? W / pool : W;
@@ -1242,7 +1242,7 @@ extern "C" int artsbir_act_pool(int dtype, const void* x, const float* bn, int r
 extern "C" int artsbir_block_out_colsum(int dtype, const void* y3, const float* bn3, const void* yd, const float* bnd,
                                         const void* identity, long long rows, int C, int nseg, void* out,
                                         unsigned char* mask_bits, float* colsum, void* stream) {
-  if (C % 8) { set_error("block_out: C %% 8 != 0"); return -1; }
+  if (C < 8 || C % 8) { set_error("block_out: C %% 8 != 0"); return -1; }
   if (nseg < 1 || rows % nseg) { set_error("block_out: %d segments do not split %lld rows", nseg, rows); return -1; }
   if (!yd && !identity) { set_error("block_out: need downsample or identity input"); return -1; }
   if (!bn3 || (yd && !bnd)) { set_error("block_out: missing BN parameter block"); return -1; }
@@ -1288,7 +1288,7 @@ extern "C" int artsbir_block_out(int dtype, const void* y3, const float* bn3, co
 }
 
 static int fill_bnb(BnBwdArgs& a, const artsbir_bn_bwd_desc* d) {
-  if (d->C % 8 || 256 % (d->C / 8 > 256 ? 1 : d->C / 8) || d->C / 8 > 256) {
+  if (d->C < 8 || d->C % 8 || 256 % (d->C / 8 > 256 ? 1 : d->C / 8) || d->C / 8 > 256) {
     set_error("bn_bwd: C=%d unsupported (need C%%8==0, C/8 dividing 256)", d->C);
     return -1;
   }
@@ -1297,7 +1297,12 @@ static int fill_bnb(BnBwdArgs& a, const artsbir_bn_bwd_desc* d) {
   if (d->kind == 1 && d->pool == 2 && (d->H % 2 || d->W % 2)) { set_error("bn_bwd: odd H/W with pool"); return -1; }
   if (d->kind < 0 || d->kind > 3) { set_error("bn_bwd: kind must be 0 .. 3"); return -1; }
   if (d->kind != 1 && d->pool > 1) { set_error("bn_bwd: pool only with kind 1"); return -1; }
-  if ((long long)d->B * d->H * d->W >= (1LL << 31)) { set_error("bn_bwd: too many pixels"); return -1; }
+  if (d->B < 1 || d->H < 1 || d->W < 1) { set_error("bn_bwd: empty geometry %dx%dx%d", d->B, d->H, d->W); return -1; }
+  // launch_bnb sizes its grid from units * nseg in int
+  if ((long long)d->B * d->H * d->W * (d->nseg > 1 ? d->nseg : 1) >= (1LL << 31)) {
+    set_error("bn_bwd: too many pixels");
+    return -1;
+  }
   a.kind = d->kind; a.pool = d->pool; a.d = d->d; a.mask = d->mask; a.mbn = d->mask_bn;
   a.ntarget = d->ntarget;
   for (int t = 0; t < 2; ++t) {
@@ -1371,6 +1376,10 @@ extern "C" int artsbir_set_deterministic(int on) {
 extern "C" int artsbir_bn_bwd_reduce(const artsbir_bn_bwd_desc* d, void* stream) {
   BnBwdArgs a;
   if (fill_bnb(a, d)) return -1;
+  if (d->kind == 1 && d->pool == 2 && d->gout) {  // the reduce stores g at one pixel per unit only
+    set_error("bn_bwd_reduce: gout with pool 2 (only the apply writes g there)");
+    return -1;
+  }
   DISPATCH_T(d->dtype, launch_bnb<T>(a, d->nseg > 1 ? d->nseg : 1, true, (hipStream_t)stream));
   ARTSBIR_CHECK_LAUNCH("bn_bwd_reduce");
   return 0;

@@ -79,6 +79,106 @@ def test_tail_entry_points_reject_bad_arguments_without_touching_the_gpu():
         _hip.call("artsbir_attnpool_fwd", _hip.DT_F32, None, None, 2, 128, 2, 129, None, None, None)
 
 
+def _bnb_desc(**kw):
+    """a BatchNorm-backward descriptor of NULL pointers with a valid geometry, then kw"""
+    import _hip
+    d = _hip.BnBwdDesc()
+    d.dtype, d.kind, d.pool, d.ntarget = _hip.DT_F32, 0, 0, 1
+    d.B, d.H, d.W, d.C, d.nseg = 2, 4, 4, 64, 1
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return d
+
+
+def test_bn_and_layout_entry_points_reject_bad_arguments_without_touching_the_gpu():
+    """the BatchNorm, element-wise and layout entry points of csrc/elementwise.hip:
+    every argument check sits ahead of the launch, so NULL pointers are never read"""
+    import _hip
+    lib = _hip.lib()
+
+    def refused(name, *args):
+        assert getattr(lib, name)(*args) != 0, (name, args)
+        return lib.artsbir_last_error()
+
+    C64 = 2 * _hip.NSLOT * 64
+    bnb = [
+        (dict(C=12), b"bn_bwd: C=12 unsupported"),            # not a multiple of 8
+        (dict(C=24), b"bn_bwd: C=24 unsupported"),            # C/8 = 3 does not divide 256
+        (dict(C=2056), b"bn_bwd: C=2056 unsupported"),        # C > 2048
+        (dict(C=0), b"bn_bwd: C=0 unsupported"),
+        (dict(ntarget=0), b"bn_bwd: ntarget must be 1 or 2"),
+        (dict(ntarget=3), b"bn_bwd: ntarget must be 1 or 2"),
+        (dict(kind=4), b"bn_bwd: kind must be 0 .. 3"),
+        (dict(kind=-1), b"bn_bwd: kind must be 0 .. 3"),
+        (dict(kind=0, pool=2), b"bn_bwd: pool only with kind 1"),
+        (dict(kind=1, pool=3), b"bn_bwd: pool must be <= 2"),
+        (dict(kind=1, pool=2, H=5), b"bn_bwd: odd H/W with pool"),
+        (dict(kind=1, pool=2, W=7), b"bn_bwd: odd H/W with pool"),
+        (dict(B=0), b"bn_bwd: empty geometry 0x4x4"),
+        (dict(nseg=3, pstride=4 * 64 - 1, cstride=3 * 64, sstride=C64), b"bn_bwd: segment strides below one parameter block"),
+        (dict(nseg=3, pstride=4 * 64, cstride=3 * 64 - 1, sstride=C64), b"bn_bwd: segment strides below one parameter block"),
+        (dict(nseg=3, pstride=4 * 64, cstride=3 * 64, sstride=C64 - 1), b"bn_bwd: segment strides below one parameter block"),
+        (dict(B=1 << 15, H=1 << 8, W=1 << 8), b"bn_bwd: too many pixels"),
+        # units * nseg is the int the launch geometry is sized from: 2^29 pixels in 4 segments
+        (dict(B=1 << 13, H=1 << 8, W=1 << 8, nseg=4, pstride=4 * 64, cstride=3 * 64, sstride=C64), b"bn_bwd: too many pixels"),
+    ]
+    for kw, msg in bnb:
+        for entry in ("artsbir_bn_bwd_reduce", "artsbir_bn_bwd_apply"):
+            assert msg in refused(entry, ctypes.byref(_bnb_desc(**kw)), None), (kw, lib.artsbir_last_error())
+    assert b"unknown dtype 7" in refused("artsbir_bn_bwd_apply", ctypes.byref(_bnb_desc(dtype=7)), None)
+    # at pool 2 the reduce writes no g (one store per quad would drop three pixels): only the apply takes gout
+    assert b"bn_bwd_reduce: gout with pool 2" in refused(
+        "artsbir_bn_bwd_reduce", ctypes.byref(_bnb_desc(kind=1, pool=2, gout=ctypes.c_void_p(64))), None)
+
+    buf = ctypes.c_void_p(64)  # a non-NULL pointer that is never read
+    for dt in (_hip.DT_F32, _hip.DT_BF16):
+        assert b"bn_stats_det: bad arguments" in refused("artsbir_bn_stats_det", dt, None, 1, 4, 8, buf, 512, None)
+        assert b"bn_stats_det: bad arguments" in refused("artsbir_bn_stats_det", dt, buf, 1, 4, 8, None, 512, None)
+        assert b"bn_stats_det: bad arguments" in refused("artsbir_bn_stats_det", dt, buf, 0, 4, 8, buf, 512, None)
+        assert b"bn_stats_det: bad arguments" in refused("artsbir_bn_stats_det", dt, buf, 1, 0, 8, buf, 512, None)
+        assert b"bn_stats_det: bad arguments" in refused("artsbir_bn_stats_det", dt, buf, 1, 4, 0, buf, 512, None)
+        assert b"bn_stats_det: seg_stride < NSLOT*2*C" in refused("artsbir_bn_stats_det", dt, buf, 2, 4, 8, buf, 511, None)
+        assert b"act_pool: C % 8" in refused("artsbir_act_pool", dt, None, None, 1, 0, 2, 4, 4, 12, 1, None, None)
+        assert b"act_pool: C % 8" in refused("artsbir_act_pool", dt, None, None, 1, 0, 2, 4, 4, 0, 1, None, None)
+        assert b"act_pool: 3 segments do not split 4 images" in refused(
+            "artsbir_act_pool", dt, None, None, 1, 0, 4, 4, 4, 8, 3, None, None)
+        assert b"act_pool: 0 segments do not split 4 images" in refused(
+            "artsbir_act_pool_colsum", dt, None, None, 1, 0, 4, 4, 4, 8, 0, None, None, None)
+        assert b"act_pool: H,W not divisible by pool" in refused(
+            "artsbir_act_pool", dt, None, None, 1, 2, 2, 5, 4, 8, 1, None, None)
+        assert b"act_pool: H,W not divisible by pool" in refused(
+            "artsbir_act_pool_colsum", dt, None, None, 1, 2, 2, 4, 7, 8, 1, None, None, None)
+        assert b"block_out: C % 8" in refused("artsbir_block_out", dt, None, buf, None, None, buf, 4, 12, 1, None, None)
+        assert b"block_out: C % 8" in refused("artsbir_block_out", dt, None, buf, None, None, buf, 4, 0, 1, None, None)
+        assert b"block_out: 3 segments do not split 4 rows" in refused(
+            "artsbir_block_out", dt, None, buf, None, None, buf, 4, 8, 3, None, None)
+        assert b"block_out: need downsample or identity input" in refused(
+            "artsbir_block_out", dt, None, buf, None, None, None, 4, 8, 1, None, None)
+        assert b"block_out: missing BN parameter block" in refused(
+            "artsbir_block_out_mask", dt, None, buf, buf, None, None, 4, 8, 1, None, None, None)
+        assert b"block_out: missing BN parameter block" in refused(
+            "artsbir_block_out_colsum", dt, None, None, None, None, buf, 4, 8, 1, None, None, None, None)
+        assert b"colsum: C and ld must be multiples of 8" in refused("artsbir_colsum", dt, None, 4, 12, 8, None, None)
+        assert b"colsum: C and ld must be multiples of 8" in refused("artsbir_colsum", dt, None, 4, 16, 12, None, None)
+        assert b"pack_input: Cin=9 > 8" in refused("artsbir_pack_input", dt, None, 1, 9, 4, 4, None, None)
+        assert b"pack_weight: ci_pad < Ci" in refused("artsbir_pack_weight", dt, None, 8, 16, 1, 1, 8, 0, 0, None, None)
+        assert b"pack_weights: n=0 nblocks=1" in refused("artsbir_pack_weights", dt, buf, 0, 1, None)
+        assert b"pack_weights: n=1 nblocks=0" in refused("artsbir_pack_weights", dt, buf, 1, 0, None)
+        assert b"pack_weights: n=1 nblocks=1" in refused("artsbir_pack_weights", dt, None, 1, 1, None)
+    assert b"cast: bad dtypes" in refused("artsbir_cast", 2, None, _hip.DT_F32, None, 8, None)
+    assert b"cast: bad dtypes" in refused("artsbir_cast", _hip.DT_BF16, None, -1, None, 8, None)
+    assert b"bn_fold: bad shape" in refused("artsbir_bn_fold", None, 4, 0, None, None, None, None, 1e-5, None, None, None)
+    assert b"bn_fold: bad shape" in refused("artsbir_bn_fold", None, 0, 4, None, None, None, None, 1e-5, None, None, None)
+    assert b"bn_finalize: train mode needs stats" in refused(
+        "artsbir_bn_finalize", None, 8, 4.0, None, None, None, None, None, 0.1, 1e-5, 1, None, None, None, None, None)
+    assert b"bn_finalize: eval mode needs running stats" in refused(
+        "artsbir_bn_finalize", buf, 8, 4.0, None, None, None, buf, None, 0.1, 1e-5, 0, None, None, None, None, None)
+    assert b"bn_bwd_finalize_seg: nseg=0" in refused(
+        "artsbir_bn_bwd_finalize_seg", None, 0, 512, 8, 4.0, None, None, 8, None, None, None, None)
+    with pytest.raises(_hip.HipError, match="bn_bwd_reduce"):
+        _hip.call("artsbir_bn_bwd_reduce", ctypes.byref(_bnb_desc(C=12)), None)
+
+
 @pytest.mark.parametrize("output_dim,count", [(1024, 38_316_896), (512, 37_267_808)])
 def test_modified_resnet_signature_keys_and_counts(output_dim, count):
     import models
