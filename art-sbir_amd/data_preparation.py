@@ -129,12 +129,18 @@ class InferenceDataset(Dataset):
         return synthetic_photo(p, self.resolution)
 
 
+def photo_number(path) -> int:
+    """the i of a synthetic photo "img{i}.jpg": its identity among the mining candidates"""
+    return int(Path(path).stem[3:])
+
+
 class SyntheticTripletDataset(Dataset):
     def __init__(self, n: int = 256, resolution: int = 224, mode: str = "train", split_ratio: float = 0.1,
                  size: float = 1.0, seed: int = 42, transform=None, dups: int = 1, name: str = None,
-                 pixels: bool = False, decode_only: bool = False):
+                 pixels: bool = False, decode_only: bool = False, ids: bool = False):
         super().__init__()
         self.pixels, self.decode_only = pixels or decode_only, decode_only
+        self.ids = ids  # items end with the positive's and the negative's photo number (in-batch mining)
         self.name = name or self.__class__.__name__
         if mode not in ("train", "test"):
             raise ValueError("invalid mode: [train, test]")
@@ -160,10 +166,14 @@ class SyntheticTripletDataset(Dataset):
     def __getitem__(self, idx):
         s, p, n = self.load_image_sketch_tuple(idx)
         if self.pixels:
-            return tuple(pixels_item(x, k, self.transform, self.decode_only)
+            item = tuple(pixels_item(x, k, self.transform, self.decode_only)
                          for x, k in ((s, "sketch"), (p, "photo"), (n, "photo")))
-        r = self.resolution
-        return synthetic_sketch(s, p, r), synthetic_photo(p, r), synthetic_photo(n, r)
+        else:
+            r = self.resolution
+            item = synthetic_sketch(s, p, r), synthetic_photo(p, r), synthetic_photo(n, r)
+        if self.ids:
+            item += tuple(torch.tensor(photo_number(x), dtype=torch.int64) for x in (p, n))
+        return item
 
     def sketch(self, idx):
         if self.pixels:
@@ -215,13 +225,15 @@ _LAST_TEST = [None]  # the gallery the Kaggle inference sketches refer to (the r
 def get_datasets(dataset: str = "Synthetic", size: float = 1.0, sketch_format: str = 'png', img_format: str = 'jpg',
                  sketch_type: str = 'placeholder', img_type: str = 'photos', split_ratio: float = 0.1, seed: int = 42,
                  transform=None, n: int = 256, resolution: int = 224, pixels: bool = False, decode_only: bool = False,
-                 **kw):
-    """pixels / decode_only: pixel mode (see synthetic_pixels above)"""
+                 ids: bool = False, **kw):
+    """pixels / decode_only: pixel mode (see synthetic_pixels above); ids: the triplet
+    items end with the positive's and the negative's photo number (int64 scalars)"""
     px = dict(pixels=pixels, decode_only=decode_only)
     if dataset.startswith("Synthetic"):
         name = None if dataset == "Synthetic" else dataset  # e.g. "SyntheticKaggleV1", "SyntheticMixedV1"
-        tr = SyntheticTripletDataset(n, resolution, "train", split_ratio, size, seed, transform, name=name, **px)
-        te = SyntheticTripletDataset(n, resolution, "test", split_ratio, size, seed, transform, name=name, **px)
+        opts = dict(px, name=name, ids=ids)
+        tr = SyntheticTripletDataset(n, resolution, "train", split_ratio, size, seed, transform, **opts)
+        te = SyntheticTripletDataset(n, resolution, "test", split_ratio, size, seed, transform, **opts)
         _LAST_TEST[0] = te
         return tr, te
     if dataset in ('KaggleInferenceV1', 'KaggleInferencedatasetV1'):

@@ -8,6 +8,8 @@
                                utils.euclidean_distance and utils.cosine_distance
   CrossEntropyLoss             nn.CrossEntropyLoss() (utils.py:57,70), mean, ignore_index=-100
   cosine_distance              1 - CosineSimilarity(dim=1, eps=1e-8)  (utils.py:31-40)
+  mine_negatives / MinedNegatives  in-batch hard / semi-hard negative mining (an addition:
+                               the reference trains on the negative the dataset drew)
 All run on the GPU kernels with explicit backward kernels.
 """
 from __future__ import annotations
@@ -206,3 +208,118 @@ class CrossEntropyLoss(nn.Module):
 
     def forward(self, logits, labels):
         return _CEFn.apply(logits, labels, int(self.ignore_index))
+
+
+# ------------------------------------------------------------ in-batch negative mining
+_MODES = {"hardest": 0, "semihard": 1}
+_METRICS = {"euclidean": 0, "cosine": 1}
+_MINE_EPS = {"euclidean": 1e-6, "cosine": 1e-8}  # the eps of TripletMarginLoss / cosine_distance
+
+
+def _mine_codes(mode, metric, eps):
+    if mode not in _MODES:
+        raise ValueError(f"mode must be one of {sorted(_MODES)}, not {mode!r}")
+    if metric not in _METRICS:
+        raise ValueError(f"metric must be one of {sorted(_METRICS)}, not {metric!r}")
+    return _MODES[mode], _METRICS[metric], float(_MINE_EPS[metric] if eps is None else eps)
+
+
+@torch.no_grad()
+def select_negatives(a, p, n, mode="hardest", metric="euclidean", eps=None, cand_ids=None):
+    """The selection alone (artsbir_mine_negatives): (sel int64 [B], d_ap [B], d_sel [B])
+    over the candidates C = [p; n].  It has no gradient."""
+    mode_c, metric_c, eps = _mine_codes(mode, metric, eps)
+    _cuda(a, p, n)
+    a, p, n = (t.detach().contiguous().float() for t in (a, p, n))
+    if not (a.dim() == 2 and a.shape == p.shape == n.shape):
+        raise ValueError(f"a, p, n must share one [B, D] shape: {tuple(a.shape)} {tuple(p.shape)} {tuple(n.shape)}")
+    B, D = a.shape
+    if cand_ids is not None:
+        _cuda(cand_ids)
+        cand_ids = cand_ids.detach().contiguous().to(torch.int64)
+        if cand_ids.shape != (2 * B,):
+            raise ValueError(f"cand_ids must have shape [{2 * B}], not {tuple(cand_ids.shape)}")
+    sel = torch.empty(B, dtype=torch.int64, device=a.device)
+    d_ap, d_sel = (torch.empty(B, dtype=torch.float32, device=a.device) for _ in range(2))
+    call("artsbir_mine_negatives", metric_c, mode_c, ptr(a), ptr(p), ptr(n), B, D, eps, ptr(cand_ids), ptr(sel),
+         ptr(d_ap), ptr(d_sel), _s())
+    return sel, d_ap, d_sel
+
+
+class _MineFn(torch.autograd.Function):
+    """N' = C[sel] with C = [p; n]; backward dC[c] = sum of dN'[i] over sel[i] == c in
+    ascending i (no atomics: two runs give the same bytes), dp = dC[:B], dn = dC[B:]"""
+
+    @staticmethod
+    def forward(ctx, a, p, n, mode, metric, eps, cand_ids):
+        sel, _, _ = select_negatives(a, p, n, mode, metric, eps, cand_ids)
+        p, n = (t.contiguous().float() for t in (p, n))
+        B, D = p.shape
+        out = torch.empty_like(p)
+        call("artsbir_rows_gather2", ptr(p), ptr(n), ptr(sel), B, D, ptr(out), _s())
+        ctx.save_for_backward(sel)
+        ctx.mark_non_differentiable(sel)
+        return out, sel
+
+    @staticmethod
+    def backward(ctx, g, _gsel):
+        sel, = ctx.saved_tensors
+        g = g.contiguous().float()
+        B, D = g.shape
+        dp, dn = torch.empty_like(g), torch.empty_like(g)
+        call("artsbir_rows_scatter2", ptr(g), ptr(sel), B, D, ptr(dp), ptr(dn), _s())
+        return None, dp, dn, None, None, None, None
+
+
+def mine_negatives(a, p, n, mode="hardest", metric="euclidean", eps=None, cand_ids=None):
+    """In-batch negative mining: for every anchor a[i] the hardest ('hardest') or the
+    semi-hardest ('semihard': the closest one farther than the positive, strictly)
+    of the 2B gallery-side rows C = [p; n], by the loss's own distance (metric
+    'euclidean': ||a - c + eps||, eps 1e-6; 'cosine': 1 - cos, eps 1e-8).  Candidate
+    c is valid for anchor i when c != i and, with cand_ids (int64 [2B], the photo of
+    every candidate), cand_ids[c] != cand_ids[i]; ties go to the lowest c; with no
+    candidate left the given negative n[i] stays (sel[i] = B + i).
+    Returns (n_mined [B, D], sel int64 [B]).  The selection has no gradient; the
+    gradient of n_mined flows to the selected rows of p and n."""
+    return _MineFn.apply(a, p, n, mode, metric, eps, cand_ids)
+
+
+class MinedNegatives(nn.Module):
+    """loss_fn with its negatives mined in the batch:
+    forward(a, p, n, *rest, cand_ids=None) = loss_fn(a, p, mine_negatives(a, p, n)[0], *rest)
+    for TripletMarginLoss, TripletMarginWithDistanceLoss and the two
+    TripletMarginLoss_with_classification composites of utils.  metric must be the
+    wrapped loss's distance.  Two device counters (no host synchronisation) follow the
+    anchors seen with gradients enabled and those whose selection is not the given
+    negative; mined_fraction() reads and resets them."""
+
+    def __init__(self, loss_fn, mode="hardest", metric="euclidean"):
+        super().__init__()
+        _mine_codes(mode, metric, None)
+        self.loss_fn, self.mode, self.metric = loss_fn, mode, metric
+        self._counts = None  # int64 [2] on the device: anchors seen, anchors mined
+        self._given = None   # arange(B, 2B) of the last batch size
+
+    margin = property(lambda self: self.loss_fn.margin)
+    classification_weight = property(lambda self: self.loss_fn.classification_weight)
+    classification_weight2 = property(lambda self: self.loss_fn.classification_weight2)
+
+    def forward(self, anchor, positive, negative, *rest, cand_ids=None):
+        mined, sel = mine_negatives(anchor, positive, negative, self.mode, self.metric, None, cand_ids)
+        if torch.is_grad_enabled():
+            B = sel.shape[0]
+            if self._counts is None or self._counts.device != sel.device:
+                self._counts = torch.zeros(2, dtype=torch.int64, device=sel.device)
+            if self._given is None or self._given.shape[0] != B or self._given.device != sel.device:
+                self._given = torch.arange(B, 2 * B, dtype=torch.int64, device=sel.device)
+            self._counts[0] += B
+            self._counts[1] += (sel != self._given).sum()
+        return self.loss_fn(anchor, positive, mined, *rest)
+
+    def mined_fraction(self) -> float:
+        """mined / seen anchors since the last call (0.0 when none was seen); resets both"""
+        if self._counts is None:
+            return 0.0
+        seen, mined = (int(v) for v in self._counts.tolist())
+        self._counts.zero_()
+        return mined / seen if seen else 0.0

@@ -16,7 +16,10 @@ Differences, all opt-in or documented:
   * data: the Sketchy/Kaggle files are not available offline — ``-d Synthetic``
     (default) generates the triplets (data_preparation.SyntheticTripletDataset);
   * one process per GPU when launched by torch.distributed.run: minibatches
-    are sharded and gradients all-reduced over RCCL (ddp.py).
+    are sharded and gradients all-reduced over RCCL (ddp.py);
+  * ``--negatives hardest|semihard`` replaces the negative the dataset drew by
+    one mined among the 2 x batch gallery-side embeddings of the step
+    (losses.MinedNegatives); every process mines in its own shard.
 """
 from __future__ import annotations
 
@@ -40,6 +43,15 @@ device = "cuda" if torch.cuda.is_available() else "cpu"
 
 
 def get_loss(loss_fn, model, elements):
+    if isinstance(loss_fn, losses.MinedNegatives):
+        # the items end with the positive's and the negative's photo number
+        # (get_datasets(ids=True)): the identities of the 2B mining candidates
+        cand_ids = torch.cat((elements[-2], elements[-1]))
+        return _get_loss(lambda *a: loss_fn(*a, cand_ids=cand_ids), model, elements[:-2])
+    return _get_loss(loss_fn, model, elements)
+
+
+def _get_loss(loss_fn, model, elements):
     # three forward calls (per-branch BatchNorm statistics, train.py:28-30), run
     # as one batched encoder pass when the model offers it
     if hasattr(model, "forward_branches") and elements[0].shape == elements[1].shape == elements[2].shape:
@@ -73,6 +85,8 @@ def _triplet_train(model, epochs, train_dataloader, test_dataloader, loss_fn, op
     start_time = timer()
     reducer = ddp.attach_overlapped_reducer(model)
     train_losses, test_losses, itrain_losses, itest_losses = [], [], [], []
+    mining = isinstance(loss_fn, losses.MinedNegatives)
+    mined_fraction = []  # per epoch: the share of training anchors whose negative was replaced
     iteration_loss_frequency = 10000 // train_dataloader.batch_size if epochs <= 6 else 0
     itest_size = max(1000 // test_dataloader.batch_size, 1)
     for epoch in range(epochs):
@@ -96,14 +110,19 @@ def _triplet_train(model, epochs, train_dataloader, test_dataloader, loss_fn, op
                 itest_losses.append(_evaluate(model, loss_fn, test_dataloader, elements if stale_eval else None,
                                               itest_size) / itest_size)
                 model.train()
+        if mining:
+            mined_fraction.append(loss_fn.mined_fraction())
         test_loss = _evaluate(model, loss_fn, test_dataloader, elements if stale_eval else None, None)
         train_losses.append(train_loss.item() / max(len(train_dataloader), 1))
         test_losses.append(test_loss / max(len(test_dataloader), 1))
         print(f"Epoch {epoch+1} - Train loss: {train_losses[epoch]:.5f} | Test loss: {test_losses[epoch]:.5f}",
               flush=True)
-    return {"train_losses": train_losses, "test_losses": test_losses, "itrain_losses": itrain_losses,
-            "itest_losses": itest_losses, "iteration_loss_frequency": iteration_loss_frequency,
-            "iteration_test_size": itest_size, "training_time": timer() - start_time}
+    out = {"train_losses": train_losses, "test_losses": test_losses, "itrain_losses": itrain_losses,
+           "itest_losses": itest_losses, "iteration_loss_frequency": iteration_loss_frequency,
+           "iteration_test_size": itest_size, "training_time": timer() - start_time}
+    if mining:
+        out["mined_fraction"] = mined_fraction
+    return out
 
 
 def _to_device(tup, model):
@@ -130,7 +149,16 @@ def _evaluate(model, loss_fn, loader, stale, limit):
     return total
 
 
-def make_loss(loss_type, with_classification, dataset_name, margin):
+def make_loss(loss_type, with_classification, dataset_name, margin, negatives='given'):
+    """the reference's loss for the configuration; negatives 'hardest' / 'semihard' wraps
+    it in losses.MinedNegatives with the metric of loss_type"""
+    loss_fn = _make_loss(loss_type, with_classification, dataset_name, margin)
+    if negatives == 'given':
+        return loss_fn
+    return losses.MinedNegatives(loss_fn, mode=negatives, metric=loss_type)
+
+
+def _make_loss(loss_type, with_classification, dataset_name, margin):
     if loss_type == 'euclidean':
         if with_classification:
             if 'Sketchy' in dataset_name:
@@ -192,6 +220,10 @@ def parse_args(argv=None):
     p.add_argument('--fresh_eval', dest='stale_eval', action='store_false',
                    help="test loss over the test batches instead of the stale train batch")
     p.add_argument('--no_save', action='store_true')
+    p.add_argument('--negatives', default='given', choices=['given', 'hardest', 'semihard'],
+                   help="the negative of every triplet: the one the dataset drew (the reference), or mined among "
+                        "the 2 x batch gallery-side embeddings of the step (losses.MinedNegatives; per process "
+                        "under torch.distributed.run: no candidates are exchanged between ranks)")
     return p.parse_args(argv)
 
 
@@ -217,7 +249,8 @@ def main(argv=None):
                                                                 transform=model.transform, n=args.synthetic_n,
                                                                 resolution=args.resolution,
                                                                 pixels=args.data_pixels or args.gpu_preprocess,
-                                                                decode_only=args.gpu_preprocess)
+                                                                decode_only=args.gpu_preprocess,
+                                                                ids=args.negatives != 'given')
     sampler = None
     if world > 1:
         sampler = torch.utils.data.distributed.DistributedSampler(train_dataset, shuffle=True)
@@ -230,12 +263,15 @@ def main(argv=None):
                              collate_fn=collate)
     optimizer = optim.Adam(model.parameters(), lr=args.learning_rate, weight_decay=args.weight_decay)
     with_classification = 'with_classification' in type(model).__name__ and 'V2' in train_dataset.state_dict['dataset']
-    loss_fn = make_loss(args.loss_type, with_classification, train_dataset.state_dict['dataset'], utils.MARGIN)
+    loss_fn = make_loss(args.loss_type, with_classification, train_dataset.state_dict['dataset'], utils.MARGIN,
+                        args.negatives)
     param_dict = {"model": args.model, "trained_layers": model.trained_layers, "dataset": args.dataset,
                   "epochs": args.epochs, "batch_size": args.batch_size, "learning_rate": args.learning_rate,
                   "weight_decay": args.weight_decay, "optimizer": type(optimizer).__name__,
                   "loss_fn": type(loss_fn).__name__, "loss_margin": loss_fn.margin, "loss_type": args.loss_type,
                   "dtype": args.dtype}
+    if args.negatives != 'given':
+        param_dict["negatives"] = args.negatives
     data_dict = train_dataset.state_dict
     print(param_dict, flush=True)
     print(data_dict, flush=True)

@@ -451,6 +451,25 @@ int artsbir_triplet_fwd(const float* a, const float* p, const float* n, int B, i
                         float* dist, float* loss, void* stream);
 int artsbir_triplet_bwd(const float* a, const float* p, const float* n, int B, int D, float margin, float eps,
                         const float* dist, const float* grad_loss, float* da, float* dp, float* dn, void* stream);
+/* In-batch negative mining (csrc/mining.hip).  a, p, n: [B][D] f32 embeddings; the
+ * candidates are C = [p; n], 2B rows (c < B: p[c], else n[c - B]).  d(i, c) is the
+ * loss's key in f32, a function of the two rows and D only: metric 0
+ * ||a[i] - C[c] + eps||_2 (eps 1e-6 in the triplet loss), metric 1 1 - cos with the
+ * clamps of artsbir_cosine_fwd (eps 1e-8).  c is valid for anchor i when c != i and,
+ * with cand_ids (int64 [2B], may be NULL), cand_ids[c] != cand_ids[i].
+ * mode 0 (hardest): the valid c of smallest d(i, c); mode 1 (semi-hard): the valid c of
+ * smallest d(i, c) among d(i, c) > d(i, i), strictly.  Ties go to the lowest c, a NaN
+ * distance is never selected, and with no candidate left sel[i] = B + i (the given
+ * negative).  Outputs: sel int64 [B], d_ap[i] = d(i, i), d_sel[i] = d(i, sel[i]).
+ * The same inputs give the same bytes on every run.  1 <= B <= 2^20, D >= 1. */
+int artsbir_mine_negatives(int metric, int mode, const float* a, const float* p, const float* n, int B, int D,
+                           float eps, const long long* cand_ids, long long* sel, float* d_ap, float* d_sel,
+                           void* stream);
+/* out[i] = C[sel[i]] ([B][D]); a sel[i] outside [0, 2B) reads nothing and gives NaN. */
+int artsbir_rows_gather2(const float* p, const float* n, const long long* sel, int B, int D, float* out, void* stream);
+/* Backward of the gather: dC[c] = sum of dout[i] over sel[i] == c in ascending i (f32,
+ * no atomics), dp = dC[:B], dn = dC[B:].  Every row is written; unselected rows are 0. */
+int artsbir_rows_scatter2(const float* dout, const long long* sel, int B, int D, float* dp, float* dn, void* stream);
 /* Adam over a device table of {param, grad, exp_avg, exp_avg_sq, numel} records
  * (host helpers size and fill the per-block table). */
 long long artsbir_adam_table_blocks(const long long* numels, int ntensors, long long chunk);
