@@ -169,6 +169,10 @@ SIGNATURES = {
     "artsbir_mine_negatives": [_c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_float, _vp, _vp, _vp, _vp, _vp],
     "artsbir_rows_gather2": [_vp, _vp, _vp, _c_int, _c_int, _vp, _vp],
     "artsbir_rows_scatter2": [_vp, _vp, _c_int, _c_int, _vp, _vp, _vp],
+    "artsbir_mine_pool": [_c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_float, _vp, _vp, _vp, _vp, _c_int, _vp, _vp,
+                          _vp, _vp],
+    "artsbir_xbm_enqueue": [_vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp],
+    "artsbir_rows_gather3": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp],
     "artsbir_adam_table_blocks": [_vp, _c_int, _c_ll],
     "artsbir_adam_fill_table": [_vp, _c_int, _c_ll, _vp],
     "artsbir_adam_step": [_vp, _vp, _c_ll, _c_ll, _c_float, _c_float, _c_float, _c_float, _c_float, _c_ll, _vp],

@@ -8,7 +8,9 @@
 //   metric 1   1 - cos with the clamps of cosine_fwd_kernel (heads.hip)
 // One wave computes a pair: lane l sums the columns l, l + 64, ... in order and the
 // 64 partial sums meet in warp_sum's butterfly, so the value depends on the two
-// rows and D alone, not on the candidate's position, the tile or the grid.
+// rows and D alone, not on the candidate's position, the tile or the grid.  The
+// routine and the key packing live in mine_dev.h, which the cross-batch memory scan
+// (xbm.hip) shares; the init / scan and final phases below are exported to it.
 //
 // Three launches:
 //   mine_init_kernel    d_ap[i] = d(i, i); sel[i] = the empty key
@@ -21,76 +23,10 @@
 //                       the same bytes every run, and ties go to the lowest c
 //   mine_final_kernel   key -> sel[i] (the given negative B + i when no candidate
 //                       qualified) and d_sel[i] = d(i, sel[i]) by the same routine
-#include "common.h"
+#include "mine_dev.h"
 #include "../../include/artsbir.h"
 
 namespace artsbir {
-
-#define MINE_TA 8            // anchors per wave of the scan
-#define MINE_MAX_B (1 << 20)
-#define MINE_EMPTY 0xFFFFFFFFFFFFFFFFull  // no real key: its distance bits would be a NaN's
-
-// f32 -> u32 that orders as the floats do (negative keys occur: 1 - cos can round below 0)
-__device__ __forceinline__ unsigned ord_f32(float d) {
-  const unsigned u = __float_as_uint(d);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// sum of squares of one row, one wave (the norm of the cosine key)
-__device__ __forceinline__ float wave_sqnorm(const float* __restrict__ r, int D, int lane) {
-  float s = 0.f;
-  for (int d = lane; d < D; d += 64) s = __fmaf_rn(r[d], r[d], s);
-  return warp_sum(s);
-}
-
-// d(anchor t, candidate) for TA anchor rows against one candidate row, one wave;
-// aa[t]: wave_sqnorm of anchor t (metric 1 only).  Every lane gets every result.
-template <int METRIC, int TA>
-__device__ __forceinline__ void wave_dist(const float* const (&ar)[TA], const float (&aa)[TA],
-                                          const float* __restrict__ cr, int D, float eps, int lane, float (&out)[TA]) {
-  float acc[TA];
-#pragma unroll
-  for (int t = 0; t < TA; ++t) acc[t] = 0.f;
-  if (METRIC == 0) {
-    for (int d = lane; d < D; d += 64) {
-      const float cv = cr[d];
-#pragma unroll
-      for (int t = 0; t < TA; ++t) {
-        const float v = ar[t][d] - cv + eps;
-        acc[t] = __fmaf_rn(v, v, acc[t]);
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < TA; ++t) out[t] = sqrtf(warp_sum(acc[t]));
-  } else {
-    float bb = 0.f;
-    for (int d = lane; d < D; d += 64) {
-      const float cv = cr[d];
-      bb = __fmaf_rn(cv, cv, bb);
-#pragma unroll
-      for (int t = 0; t < TA; ++t) acc[t] = __fmaf_rn(ar[t][d], cv, acc[t]);
-    }
-    const float nb = fmaxf(sqrtf(warp_sum(bb)), eps);
-#pragma unroll
-    for (int t = 0; t < TA; ++t) out[t] = 1.f - warp_sum(acc[t]) / (fmaxf(sqrtf(aa[t]), eps) * nb);
-  }
-}
-
-// candidate c of C = [P; N]
-__device__ __forceinline__ const float* cand_row(const float* __restrict__ p, const float* __restrict__ n, int B, int D,
-                                                 int c) {
-  return c < B ? p + (long long)c * D : n + (long long)(c - B) * D;
-}
-
-template <int METRIC>
-__device__ __forceinline__ float wave_dist1(const float* __restrict__ ar, const float* __restrict__ cr, int D, float eps,
-                                            int lane) {
-  const float* const rows[1] = {ar};
-  float aa[1] = {0.f}, out[1];
-  if (METRIC == 1) aa[0] = wave_sqnorm(ar, D, lane);
-  wave_dist<METRIC, 1>(rows, aa, cr, D, eps, lane, out);
-  return out[0];
-}
 
 // one wave per anchor
 template <int METRIC>
@@ -133,14 +69,7 @@ __global__ void __launch_bounds__(256) mine_scan_kernel(int mode, const float* _
     float d[MINE_TA];
     wave_dist<METRIC, MINE_TA>(rows, aa, cand_row(p, n, B, D, c), D, eps, lane, d);
     const long long cid = cand_ids ? cand_ids[c] : 0;
-#pragma unroll
-    for (int t = 0; t < MINE_TA; ++t) {
-      bool ok = c != i0 + t && d[t] == d[t];  // never the anchor's own positive, never a NaN
-      if (cand_ids) ok = ok && cid != aid[t];
-      if (mode == 1) ok = ok && d[t] > dap[t];
-      const unsigned long long k = ((unsigned long long)ord_f32(d[t]) << 32) | (unsigned)c;
-      if (ok && k < best[t]) best[t] = k;
-    }
+    mine_update<MINE_TA>(mode, c, i0, d, dap, cand_ids != nullptr, cid, aid, best);
   }
   if (lane == 0) {
 #pragma unroll
@@ -149,17 +78,18 @@ __global__ void __launch_bounds__(256) mine_scan_kernel(int mode, const float* _
   }
 }
 
-// one wave per anchor
+// one wave per anchor; a key's c >= 2B is a slot of the cross-batch memory mem (xbm.hip)
 template <int METRIC>
 __global__ void __launch_bounds__(256) mine_final_kernel(const float* __restrict__ a, const float* __restrict__ p,
-                                                         const float* __restrict__ n, int B, int D, float eps,
-                                                         long long* __restrict__ sel, float* __restrict__ d_sel) {
+                                                         const float* __restrict__ n, const float* __restrict__ mem,
+                                                         int B, int D, float eps, long long* __restrict__ sel,
+                                                         float* __restrict__ d_sel) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= B) return;
   const unsigned long long k = ((const unsigned long long*)sel)[i];
   const int c = k == MINE_EMPTY ? B + i : (int)(unsigned)k;
-  const float d = wave_dist1<METRIC>(a + (long long)i * D, cand_row(p, n, B, D, c), D, eps, lane);
+  const float d = wave_dist1<METRIC>(a + (long long)i * D, pool_row(p, n, mem, B, D, c), D, eps, lane);
   if (lane == 0) { sel[i] = c; d_sel[i] = d; }
 }
 
@@ -212,11 +142,7 @@ __global__ void __launch_bounds__(256) rows_scatter2_kernel(const float* __restr
   }
 }
 
-}  // namespace artsbir
-
-using namespace artsbir;
-
-static bool mine_shape_ok(const char* name, int B, int D) {
+bool mine_shape_ok(const char* name, int B, int D) {
   if (B < 1) { set_error("%s: B=%d must be >= 1", name, B); return false; }
   if (D < 1) { set_error("%s: D=%d must be >= 1", name, D); return false; }
   if (B > MINE_MAX_B) { set_error("%s: B=%d above 2^20", name, B); return false; }
@@ -224,8 +150,8 @@ static bool mine_shape_ok(const char* name, int B, int D) {
 }
 
 template <int METRIC>
-static void mine_launch(int mode, const float* a, const float* p, const float* n, int B, int D, float eps,
-                        const long long* cand_ids, long long* sel, float* d_ap, float* d_sel, hipStream_t st) {
+static void mine_batch(int mode, const float* a, const float* p, const float* n, int B, int D, float eps,
+                       const long long* cand_ids, long long* sel, float* d_ap, hipStream_t st) {
   unsigned long long* key = (unsigned long long*)sel;
   const unsigned rows4 = (unsigned)((B + 3) / 4);
   const int ntile = (B + MINE_TA - 1) / MINE_TA;
@@ -237,8 +163,26 @@ static void mine_launch(int mode, const float* a, const float* p, const float* n
   hipLaunchKernelGGL(mine_init_kernel<METRIC>, dim3(rows4), dim3(256), 0, st, a, p, B, D, eps, key, d_ap);
   hipLaunchKernelGGL(mine_scan_kernel<METRIC>, dim3((unsigned)ntile, (unsigned)ny), dim3(256), 0, st, mode, a, p, n, B, D,
                      eps, cand_ids, d_ap, key);
-  hipLaunchKernelGGL(mine_final_kernel<METRIC>, dim3(rows4), dim3(256), 0, st, a, p, n, B, D, eps, sel, d_sel);
 }
+
+void mine_launch_batch(int metric, int mode, const float* a, const float* p, const float* n, int B, int D, float eps,
+                       const long long* cand_ids, long long* sel, float* d_ap, hipStream_t st) {
+  if (metric == 0) mine_batch<0>(mode, a, p, n, B, D, eps, cand_ids, sel, d_ap, st);
+  else mine_batch<1>(mode, a, p, n, B, D, eps, cand_ids, sel, d_ap, st);
+}
+
+void mine_launch_final(int metric, const float* a, const float* p, const float* n, const float* mem, int B, int D,
+                       float eps, long long* sel, float* d_sel, hipStream_t st) {
+  const unsigned rows4 = (unsigned)((B + 3) / 4);
+  if (metric == 0)
+    hipLaunchKernelGGL(mine_final_kernel<0>, dim3(rows4), dim3(256), 0, st, a, p, n, mem, B, D, eps, sel, d_sel);
+  else
+    hipLaunchKernelGGL(mine_final_kernel<1>, dim3(rows4), dim3(256), 0, st, a, p, n, mem, B, D, eps, sel, d_sel);
+}
+
+}  // namespace artsbir
+
+using namespace artsbir;
 
 extern "C" int artsbir_mine_negatives(int metric, int mode, const float* a, const float* p, const float* n, int B, int D,
                                       float eps, const long long* cand_ids, long long* sel, float* d_ap, float* d_sel,
@@ -248,8 +192,8 @@ extern "C" int artsbir_mine_negatives(int metric, int mode, const float* a, cons
   if (mode != 0 && mode != 1) { set_error("mine_negatives: mode=%d outside {0, 1}", mode); return -1; }
   if (!a || !p || !n || !sel || !d_ap || !d_sel) { set_error("mine_negatives: NULL pointer"); return -1; }
   hipStream_t st = (hipStream_t)stream;
-  if (metric == 0) mine_launch<0>(mode, a, p, n, B, D, eps, cand_ids, sel, d_ap, d_sel, st);
-  else mine_launch<1>(mode, a, p, n, B, D, eps, cand_ids, sel, d_ap, d_sel, st);
+  mine_launch_batch(metric, mode, a, p, n, B, D, eps, cand_ids, sel, d_ap, st);
+  mine_launch_final(metric, a, p, n, nullptr, B, D, eps, sel, d_sel, st);
   ARTSBIR_CHECK_LAUNCH("mine_negatives");
   return 0;
 }

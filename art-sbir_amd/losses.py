@@ -10,6 +10,8 @@
   cosine_distance              1 - CosineSimilarity(dim=1, eps=1e-8)  (utils.py:31-40)
   mine_negatives / MinedNegatives  in-batch hard / semi-hard negative mining (an addition:
                                the reference trains on the negative the dataset drew)
+  CrossBatchMemory             a ring of past gallery-side embeddings on the device that the
+                               mining above can search as well (an addition)
 All run on the GPU kernels with explicit backward kernels.
 """
 from __future__ import annotations
@@ -224,10 +226,89 @@ def _mine_codes(mode, metric, eps):
     return _MODES[mode], _METRICS[metric], float(_MINE_EPS[metric] if eps is None else eps)
 
 
+def _gather_ranks(rows, ids):
+    """(rows, ids) of every rank, rank-major, identical on all ranks: all_gather_into_tensor
+    under an initialised process group of more than one rank, the arguments otherwise.
+    ids may be None, on every rank alike."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return rows, ids
+    world = dist.get_world_size()
+    rows = rows.contiguous()
+    all_rows = rows.new_empty((world * rows.shape[0],) + tuple(rows.shape[1:]))
+    dist.all_gather_into_tensor(all_rows, rows)
+    if ids is None:
+        return all_rows, None
+    ids = ids.contiguous()
+    all_ids = ids.new_empty(world * ids.shape[0])
+    dist.all_gather_into_tensor(all_ids, ids)
+    return all_rows, all_ids
+
+
+class CrossBatchMemory:
+    """A ring of the last `size` gallery-side embeddings on the device (Wang et al.,
+    "Cross-Batch Memory for Embedding Learning", CVPR 2020) for select_negatives /
+    mine_negatives / MinedNegatives(memory=...): mem f32 [size, dim], mem_ids int64 [size]
+    (the photo of every row; -1: none) and mem_state int64 [2] = (head, count).  Plain
+    tensors: no checkpoint holds them.  The state lives on the device and only kernels
+    read and write it (artsbir_xbm_enqueue, artsbir_mine_pool); rows in the ring are
+    constants: no gradient reaches them.  dim None: the width (and, with device None, the
+    device) of the first rows it meets, allocated then."""
+
+    def __init__(self, size, dim, device=None):
+        size = int(size)
+        if size < 1 or (dim is not None and int(dim) < 1):
+            raise ValueError(f"CrossBatchMemory needs size >= 1 and dim >= 1, not {size} x {dim}")
+        self.size, self.dim, self.mem, self.mem_ids, self.mem_state = size, None, None, None, None
+        if dim is not None:
+            self._allocate(int(dim), torch.device("cuda" if device is None else device))
+        self._device = device
+
+    def _allocate(self, dim, device):
+        self.dim = dim
+        self.mem = torch.zeros(self.size, dim, dtype=torch.float32, device=device)
+        self.mem_ids = torch.full((self.size,), -1, dtype=torch.int64, device=device)
+        self.mem_state = torch.zeros(2, dtype=torch.int64, device=device)
+
+    def _ready(self, rows):
+        """allocated, and of the width and on the device of rows [*, dim]"""
+        if self.mem is None:
+            self._allocate(rows.shape[1], rows.device if self._device is None else torch.device(self._device))
+        if rows.dim() != 2 or self.dim != rows.shape[1] or self.mem.device != rows.device:
+            raise ValueError(f"the memory holds rows of width {self.dim} on {self.mem.device}, not "
+                             f"{tuple(rows.shape)} on {rows.device}")
+
+    @torch.no_grad()
+    def enqueue(self, rows, ids=None):
+        """rows [R, dim] (ids int64 [R] or None) into the ring, row r at slot (head + r) mod
+        size; with more than one rank every rank's rows first, rank-major"""
+        _cuda(rows)
+        rows = rows.detach().contiguous().float()
+        self._ready(rows)
+        if ids is not None:
+            _cuda(ids)
+            ids = ids.detach().contiguous().to(torch.int64)
+            if ids.shape != (rows.shape[0],):
+                raise ValueError(f"ids must have shape [{rows.shape[0]}], not {tuple(ids.shape)}")
+        rows, ids = _gather_ranks(rows, ids)
+        call("artsbir_xbm_enqueue", ptr(rows), ptr(ids), rows.shape[0], self.dim, ptr(self.mem), ptr(self.mem_ids),
+             ptr(self.mem_state), self.size, _s())
+
+    def reset(self):
+        """forget every row: head = count = 0, on the device"""
+        if self.mem_state is not None:
+            self.mem_state.zero_()
+
+    def filled(self) -> int:
+        """slots that hold a row.  For debugging only: it synchronises with the device."""
+        return 0 if self.mem_state is None else min(int(self.mem_state[1].item()), self.size)
+
+
 @torch.no_grad()
-def select_negatives(a, p, n, mode="hardest", metric="euclidean", eps=None, cand_ids=None):
-    """The selection alone (artsbir_mine_negatives): (sel int64 [B], d_ap [B], d_sel [B])
-    over the candidates C = [p; n].  It has no gradient."""
+def select_negatives(a, p, n, mode="hardest", metric="euclidean", eps=None, cand_ids=None, memory=None):
+    """The selection alone: (sel int64 [B], d_ap [B], d_sel [B]) over the candidates
+    C = [p; n] (artsbir_mine_negatives) and, with a CrossBatchMemory, its filled slots as
+    the candidates 2B + j (artsbir_mine_pool).  It has no gradient."""
     mode_c, metric_c, eps = _mine_codes(mode, metric, eps)
     _cuda(a, p, n)
     a, p, n = (t.detach().contiguous().float() for t in (a, p, n))
@@ -241,22 +322,34 @@ def select_negatives(a, p, n, mode="hardest", metric="euclidean", eps=None, cand
             raise ValueError(f"cand_ids must have shape [{2 * B}], not {tuple(cand_ids.shape)}")
     sel = torch.empty(B, dtype=torch.int64, device=a.device)
     d_ap, d_sel = (torch.empty(B, dtype=torch.float32, device=a.device) for _ in range(2))
-    call("artsbir_mine_negatives", metric_c, mode_c, ptr(a), ptr(p), ptr(n), B, D, eps, ptr(cand_ids), ptr(sel),
-         ptr(d_ap), ptr(d_sel), _s())
+    if memory is None:
+        call("artsbir_mine_negatives", metric_c, mode_c, ptr(a), ptr(p), ptr(n), B, D, eps, ptr(cand_ids), ptr(sel),
+             ptr(d_ap), ptr(d_sel), _s())
+    else:
+        memory._ready(a)
+        call("artsbir_mine_pool", metric_c, mode_c, ptr(a), ptr(p), ptr(n), B, D, eps, ptr(cand_ids),
+             ptr(memory.mem), ptr(memory.mem_ids), ptr(memory.mem_state), memory.size, ptr(sel), ptr(d_ap),
+             ptr(d_sel), _s())
     return sel, d_ap, d_sel
 
 
 class _MineFn(torch.autograd.Function):
     """N' = C[sel] with C = [p; n]; backward dC[c] = sum of dN'[i] over sel[i] == c in
-    ascending i (no atomics: two runs give the same bytes), dp = dC[:B], dn = dC[B:]"""
+    ascending i (no atomics: two runs give the same bytes), dp = dC[:B], dn = dC[B:].
+    With a memory sel[i] >= 2B takes N'[i] from the ring: a constant, so it adds to no
+    row of dC."""
 
     @staticmethod
-    def forward(ctx, a, p, n, mode, metric, eps, cand_ids):
-        sel, _, _ = select_negatives(a, p, n, mode, metric, eps, cand_ids)
+    def forward(ctx, a, p, n, mode, metric, eps, cand_ids, memory):
+        sel, _, _ = select_negatives(a, p, n, mode, metric, eps, cand_ids, memory)
         p, n = (t.contiguous().float() for t in (p, n))
         B, D = p.shape
         out = torch.empty_like(p)
-        call("artsbir_rows_gather2", ptr(p), ptr(n), ptr(sel), B, D, ptr(out), _s())
+        if memory is None:
+            call("artsbir_rows_gather2", ptr(p), ptr(n), ptr(sel), B, D, ptr(out), _s())
+        else:
+            call("artsbir_rows_gather3", ptr(p), ptr(n), ptr(memory.mem), ptr(sel), B, D, memory.size, ptr(out),
+                 _s())
         ctx.save_for_backward(sel)
         ctx.mark_non_differentiable(sel)
         return out, sel
@@ -268,10 +361,10 @@ class _MineFn(torch.autograd.Function):
         B, D = g.shape
         dp, dn = torch.empty_like(g), torch.empty_like(g)
         call("artsbir_rows_scatter2", ptr(g), ptr(sel), B, D, ptr(dp), ptr(dn), _s())
-        return None, dp, dn, None, None, None, None
+        return None, dp, dn, None, None, None, None, None
 
 
-def mine_negatives(a, p, n, mode="hardest", metric="euclidean", eps=None, cand_ids=None):
+def mine_negatives(a, p, n, mode="hardest", metric="euclidean", eps=None, cand_ids=None, memory=None):
     """In-batch negative mining: for every anchor a[i] the hardest ('hardest') or the
     semi-hardest ('semihard': the closest one farther than the positive, strictly)
     of the 2B gallery-side rows C = [p; n], by the loss's own distance (metric
@@ -279,9 +372,13 @@ def mine_negatives(a, p, n, mode="hardest", metric="euclidean", eps=None, cand_i
     c is valid for anchor i when c != i and, with cand_ids (int64 [2B], the photo of
     every candidate), cand_ids[c] != cand_ids[i]; ties go to the lowest c; with no
     candidate left the given negative n[i] stays (sel[i] = B + i).
+    With memory (a CrossBatchMemory) its filled slots are candidates too: c = 2B + j
+    is slot j, valid unless memory.mem_ids[j] == cand_ids[i]; a batch row wins a tie
+    against a ring row and a lower slot against a higher one.
     Returns (n_mined [B, D], sel int64 [B]).  The selection has no gradient; the
-    gradient of n_mined flows to the selected rows of p and n."""
-    return _MineFn.apply(a, p, n, mode, metric, eps, cand_ids)
+    gradient of n_mined flows to the selected rows of p and n, and to nothing where
+    the selection is a ring slot."""
+    return _MineFn.apply(a, p, n, mode, metric, eps, cand_ids, memory)
 
 
 class MinedNegatives(nn.Module):
@@ -289,15 +386,20 @@ class MinedNegatives(nn.Module):
     forward(a, p, n, *rest, cand_ids=None) = loss_fn(a, p, mine_negatives(a, p, n)[0], *rest)
     for TripletMarginLoss, TripletMarginWithDistanceLoss and the two
     TripletMarginLoss_with_classification composites of utils.  metric must be the
-    wrapped loss's distance.  Two device counters (no host synchronisation) follow the
-    anchors seen with gradients enabled and those whose selection is not the given
-    negative; mined_fraction() reads and resets them."""
+    wrapped loss's distance.  Device counters (no host synchronisation) follow the
+    anchors seen with gradients enabled, those whose selection is not the given
+    negative and those whose selection is a slot of the memory; mined_fraction() and
+    memory_fraction() read them and reset their own.
+    memory (a CrossBatchMemory, default None): with gradients enabled the negatives are
+    mined over the batch and the ring, and cat(p, n).detach() with cand_ids is enqueued
+    after the selection, so a step never meets its own rows in the ring; under
+    torch.no_grad() the ring is neither read nor written."""
 
-    def __init__(self, loss_fn, mode="hardest", metric="euclidean"):
+    def __init__(self, loss_fn, mode="hardest", metric="euclidean", memory=None):
         super().__init__()
         _mine_codes(mode, metric, None)
-        self.loss_fn, self.mode, self.metric = loss_fn, mode, metric
-        self._counts = None  # int64 [2] on the device: anchors seen, anchors mined
+        self.loss_fn, self.mode, self.metric, self.memory = loss_fn, mode, metric, memory
+        self._counts = None  # int64 [4] on the device: anchors seen, mined | seen, from the memory
         self._given = None   # arange(B, 2B) of the last batch size
 
     margin = property(lambda self: self.loss_fn.margin)
@@ -305,21 +407,34 @@ class MinedNegatives(nn.Module):
     classification_weight2 = property(lambda self: self.loss_fn.classification_weight2)
 
     def forward(self, anchor, positive, negative, *rest, cand_ids=None):
-        mined, sel = mine_negatives(anchor, positive, negative, self.mode, self.metric, None, cand_ids)
+        memory = self.memory if torch.is_grad_enabled() else None
+        mined, sel = mine_negatives(anchor, positive, negative, self.mode, self.metric, None, cand_ids, memory)
         if torch.is_grad_enabled():
             B = sel.shape[0]
             if self._counts is None or self._counts.device != sel.device:
-                self._counts = torch.zeros(2, dtype=torch.int64, device=sel.device)
+                self._counts = torch.zeros(4, dtype=torch.int64, device=sel.device)
             if self._given is None or self._given.shape[0] != B or self._given.device != sel.device:
                 self._given = torch.arange(B, 2 * B, dtype=torch.int64, device=sel.device)
             self._counts[0] += B
             self._counts[1] += (sel != self._given).sum()
+            if memory is not None:
+                self._counts[2] += B
+                self._counts[3] += (sel >= 2 * B).sum()
+                memory.enqueue(torch.cat((positive, negative)).detach(), cand_ids)
         return self.loss_fn(anchor, positive, mined, *rest)
+
+    def _fraction(self, k) -> float:
+        if self._counts is None:
+            return 0.0
+        seen, hit = (int(v) for v in self._counts[k:k + 2].tolist())
+        self._counts[k:k + 2].zero_()
+        return hit / seen if seen else 0.0
 
     def mined_fraction(self) -> float:
         """mined / seen anchors since the last call (0.0 when none was seen); resets both"""
-        if self._counts is None:
-            return 0.0
-        seen, mined = (int(v) for v in self._counts.tolist())
-        self._counts.zero_()
-        return mined / seen if seen else 0.0
+        return self._fraction(0)
+
+    def memory_fraction(self) -> float:
+        """anchors whose selection is a slot of the memory / anchors seen with the memory
+        since the last call (0.0 when none was seen); resets both"""
+        return self._fraction(2)

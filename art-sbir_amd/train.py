@@ -19,7 +19,10 @@ Differences, all opt-in or documented:
     are sharded and gradients all-reduced over RCCL (ddp.py);
   * ``--negatives hardest|semihard`` replaces the negative the dataset drew by
     one mined among the 2 x batch gallery-side embeddings of the step
-    (losses.MinedNegatives); every process mines in its own shard.
+    (losses.MinedNegatives); every process mines in its own shard;
+  * ``--memory_size M`` adds a ring of the last M gallery-side embeddings to the
+    candidates of ``--negatives`` (losses.CrossBatchMemory); under
+    torch.distributed.run the ring holds every rank's rows, so negatives cross ranks.
 """
 from __future__ import annotations
 
@@ -87,6 +90,8 @@ def _triplet_train(model, epochs, train_dataloader, test_dataloader, loss_fn, op
     train_losses, test_losses, itrain_losses, itest_losses = [], [], [], []
     mining = isinstance(loss_fn, losses.MinedNegatives)
     mined_fraction = []  # per epoch: the share of training anchors whose negative was replaced
+    with_memory = mining and loss_fn.memory is not None
+    memory_fraction = []  # per epoch: the share whose negative came from the cross-batch memory
     iteration_loss_frequency = 10000 // train_dataloader.batch_size if epochs <= 6 else 0
     itest_size = max(1000 // test_dataloader.batch_size, 1)
     for epoch in range(epochs):
@@ -112,6 +117,8 @@ def _triplet_train(model, epochs, train_dataloader, test_dataloader, loss_fn, op
                 model.train()
         if mining:
             mined_fraction.append(loss_fn.mined_fraction())
+        if with_memory:
+            memory_fraction.append(loss_fn.memory_fraction())
         test_loss = _evaluate(model, loss_fn, test_dataloader, elements if stale_eval else None, None)
         train_losses.append(train_loss.item() / max(len(train_dataloader), 1))
         test_losses.append(test_loss / max(len(test_dataloader), 1))
@@ -122,6 +129,8 @@ def _triplet_train(model, epochs, train_dataloader, test_dataloader, loss_fn, op
            "iteration_test_size": itest_size, "training_time": timer() - start_time}
     if mining:
         out["mined_fraction"] = mined_fraction
+    if with_memory:
+        out["memory_fraction"] = memory_fraction
     return out
 
 
@@ -149,13 +158,25 @@ def _evaluate(model, loss_fn, loader, stale, limit):
     return total
 
 
-def make_loss(loss_type, with_classification, dataset_name, margin, negatives='given'):
+def make_loss(loss_type, with_classification, dataset_name, margin, negatives='given', memory_size=0):
     """the reference's loss for the configuration; negatives 'hardest' / 'semihard' wraps
-    it in losses.MinedNegatives with the metric of loss_type"""
+    it in losses.MinedNegatives with the metric of loss_type, memory_size > 0 gives that a
+    losses.CrossBatchMemory of memory_size rows (of the embeddings' width, allocated at the
+    first step)"""
+    _check_memory_size(memory_size, negatives)
     loss_fn = _make_loss(loss_type, with_classification, dataset_name, margin)
     if negatives == 'given':
         return loss_fn
-    return losses.MinedNegatives(loss_fn, mode=negatives, metric=loss_type)
+    memory = losses.CrossBatchMemory(memory_size, None) if memory_size else None
+    return losses.MinedNegatives(loss_fn, mode=negatives, metric=loss_type, memory=memory)
+
+
+def _check_memory_size(memory_size, negatives):
+    if memory_size < 0:
+        raise SystemExit(f"--memory_size {memory_size} must be >= 0")
+    if memory_size and negatives == 'given':
+        raise SystemExit("--memory_size needs --negatives hardest or semihard: the memory only adds candidates "
+                         "to the mining")
 
 
 def _make_loss(loss_type, with_classification, dataset_name, margin):
@@ -223,8 +244,15 @@ def parse_args(argv=None):
     p.add_argument('--negatives', default='given', choices=['given', 'hardest', 'semihard'],
                    help="the negative of every triplet: the one the dataset drew (the reference), or mined among "
                         "the 2 x batch gallery-side embeddings of the step (losses.MinedNegatives; per process "
-                        "under torch.distributed.run: no candidates are exchanged between ranks)")
-    return p.parse_args(argv)
+                        "under torch.distributed.run: the step's candidates are not exchanged between ranks, "
+                        "--memory_size adds past rows of every rank)")
+    p.add_argument('--memory_size', type=int, default=0,
+                   help="cross-batch memory: also mine among the last M gallery-side embeddings of earlier steps, "
+                        "of every rank under torch.distributed.run (losses.CrossBatchMemory; 0 = off; needs "
+                        "--negatives hardest or semihard)")
+    args = p.parse_args(argv)
+    _check_memory_size(args.memory_size, args.negatives)
+    return args
 
 
 def main(argv=None):
@@ -264,7 +292,7 @@ def main(argv=None):
     optimizer = optim.Adam(model.parameters(), lr=args.learning_rate, weight_decay=args.weight_decay)
     with_classification = 'with_classification' in type(model).__name__ and 'V2' in train_dataset.state_dict['dataset']
     loss_fn = make_loss(args.loss_type, with_classification, train_dataset.state_dict['dataset'], utils.MARGIN,
-                        args.negatives)
+                        args.negatives, args.memory_size)
     param_dict = {"model": args.model, "trained_layers": model.trained_layers, "dataset": args.dataset,
                   "epochs": args.epochs, "batch_size": args.batch_size, "learning_rate": args.learning_rate,
                   "weight_decay": args.weight_decay, "optimizer": type(optimizer).__name__,
@@ -272,6 +300,8 @@ def main(argv=None):
                   "dtype": args.dtype}
     if args.negatives != 'given':
         param_dict["negatives"] = args.negatives
+    if args.memory_size:
+        param_dict["memory_size"] = args.memory_size
     data_dict = train_dataset.state_dict
     print(param_dict, flush=True)
     print(data_dict, flush=True)

@@ -470,6 +470,30 @@ int artsbir_rows_gather2(const float* p, const float* n, const long long* sel, i
 /* Backward of the gather: dC[c] = sum of dout[i] over sel[i] == c in ascending i (f32,
  * no atomics), dp = dC[:B], dn = dC[B:].  Every row is written; unselected rows are 0. */
 int artsbir_rows_scatter2(const float* dout, const long long* sel, int B, int D, float* dp, float* dn, void* stream);
+/* Cross-batch memory (csrc/xbm.hip; an addition to the step of train.py:59-70, as the
+ * mining above): a ring of the last M gallery-side embeddings on the device, mem f32
+ * [M][D], mem_ids int64 [M] (the photo of every row, -1: none) and mem_state int64 [2] =
+ * {head, count}, read and written by the kernels only.
+ * artsbir_mine_pool is artsbir_mine_negatives over the batch and the ring: c in [0, 2B) is
+ * C = [p; n], c = 2B + j is slot j, a candidate when j < min(count, M) and, with cand_ids,
+ * mem_ids[j] != cand_ids[i].  Same key (a pair gives the same bits wherever its row
+ * lives), same modes, ties to the lowest c, NaN never selected, sel[i] = B + i with no
+ * candidate; sel in [0, 2B + M).  With M = 0, mem NULL or count = 0 the outputs are the
+ * bytes of artsbir_mine_negatives.  0 <= M <= 2^24; mem needs mem_ids and mem_state. */
+int artsbir_mine_pool(int metric, int mode, const float* a, const float* p, const float* n, int B, int D, float eps,
+                      const long long* cand_ids, const float* mem, const long long* mem_ids,
+                      const long long* mem_state, int M, long long* sel, float* d_ap, float* d_sel, void* stream);
+/* rows [R][D] (ids int64 [R] or NULL) into the ring: row r goes to slot (head + r) mod M
+ * (R > M: only the last M rows are kept), then, as a device operation of its own in
+ * stream order, head = (head + R) mod M and count = min(count + R, M).
+ * 1 <= R <= 2^24, 1 <= M <= 2^24. */
+int artsbir_xbm_enqueue(const float* rows, const long long* ids, int R, int D, float* mem, long long* mem_ids,
+                        long long* mem_state, int M, void* stream);
+/* out[i] = C[sel[i]] for sel[i] < 2B, mem[sel[i] - 2B] otherwise; a sel[i] outside
+ * [0, 2B + M) reads nothing and gives NaN.  Its backward is artsbir_rows_scatter2: a
+ * selection >= 2B is a constant and adds to no row. */
+int artsbir_rows_gather3(const float* p, const float* n, const float* mem, const long long* sel, int B, int D, int M,
+                         float* out, void* stream);
 /* Adam over a device table of {param, grad, exp_avg, exp_avg_sq, numel} records
  * (host helpers size and fill the per-block table). */
 long long artsbir_adam_table_blocks(const long long* numels, int ntensors, long long chunk);

@@ -2,9 +2,11 @@
 """The C2 training step (ResNet-50, 512-d, bf16, 384 triplets, bench.py's model,
 batch and tuning table) through train.triplet_train with the given negatives and
 with --negatives hardest / semihard, alternating on the same device: ms per step
-from device events recorded as the loop fetches each batch.
+from device events recorded as the loop fetches each batch.  With --memory_size M the
+forms are --negatives hardest alone and with a cross-batch memory of M rows, filled
+with random rows ahead of the first step so that every timed step scans all M.
 
-    python tools/mining_step.py [--steps 10] [--warmup 3] [--out FILE]"""
+    python tools/mining_step.py [--steps 10] [--warmup 3] [--memory_size M] [--out FILE]"""
 import argparse
 import os
 import statistics
@@ -41,14 +43,16 @@ class ResidentLoader:
             yield self.batch
 
 
-def run(negatives, batch, args, dev):
+def run(negatives, batch, args, dev, memory_size=0):
     torch.manual_seed(1234)
     model = models.ModifiedResNet(bench.LAYERS, bench.OUT_DIM, heads=bench.HEADS, input_resolution=bench.RES,
                                   width=bench.WIDTH).to(dev)
     model.compute_dtype = torch.bfloat16
     opt = optim.Adam(model.parameters(), lr=1e-5, weight_decay=0.002)
-    loss_fn = train.make_loss("euclidean", False, "Synthetic", 0.2, negatives)
+    loss_fn = train.make_loss("euclidean", False, "Synthetic", 0.2, negatives, memory_size)
     B = batch[0].shape[0]
+    if memory_size:  # a full ring from the first step on (768 rows a step would take M / 768 steps)
+        loss_fn.memory.enqueue(torch.randn(memory_size, bench.OUT_DIM, device=dev))
     if negatives != "given":
         batch = batch + [torch.arange(B, device=dev), torch.arange(B, 2 * B, device=dev)]
     loader = ResidentLoader(batch, args.warmup + args.steps + 1, B)
@@ -65,6 +69,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=384)
     ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--memory_size", type=int, default=0)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -80,10 +85,15 @@ def main():
     std = torch.tensor(models.CLIP_STD, device=dev)[None, :, None, None]
     batch = [((t - mean) / std).contiguous() for t in (sketch, pos, neg)]
     lines = []
+    forms = [("given", 0), ("hardest", 0), ("semihard", 0)]
+    if args.memory_size:
+        forms = [("hardest", 0), ("hardest", args.memory_size)]
     for r in range(args.rounds):
-        for negatives in ("given", "hardest", "semihard"):
-            med, best, out = run(negatives, batch, args, dev)
+        for negatives, memory_size in forms:
+            med, best, out = run(negatives, batch, args, dev, memory_size)
             extra = f" mined_fraction={out['mined_fraction'][0]:.3f}" if "mined_fraction" in out else ""
+            if "memory_fraction" in out:
+                extra += f" memory_size={memory_size} memory_fraction={out['memory_fraction'][0]:.3f}"
             lines.append(f"C2 step B={B} round={r} negatives={negatives:<8s} median={med:.2f} ms min={best:.2f} ms "
                          f"over {args.steps} steps train_loss={out['train_losses'][0]:.5f}{extra}")
             print(lines[-1], flush=True)
