@@ -642,10 +642,9 @@ static void launch_conv_old(const ConvArgs& a, hipStream_t st) {
 
 // ---------------------------------------------------------------------------
 // Kernel choice per shape (bf16), tuned on first use (tune.h).
-//   Convolutions: the register-staged kernel above (-2), the pipelined LDS-DMA
-//   kernel's tile shapes (0..4) or the persistent streaming kernel (10),
-//   pgemm.hip.  The trial runs write the output to the real buffers and the BN
-//   statistics to a scratch buffer; ARTSBIR_TUNE=0 uses the static heuristic,
+//   Convolutions: the register-staged kernel above (-2) or a candidate of the
+//   pipelined LDS-DMA kernels (ids: pgemm.h).  The trial runs write the
+//   output to the real buffers and the BN statistics to a scratch buffer; ARTSBIR_TUNE=0 uses the static heuristic,
 //   ARTSBIR_PGEMM_CFG=<c> forces candidate c (tests).
 //   Weight gradients: the register-staged wgrad_kernel (-1) or a tile
 //   configuration c >= 0 of the pipelined LDS-DMA transposed-read kernel
@@ -783,9 +782,7 @@ static int tune_conv(const ConvArgs& a, const PgArgs& p, hipStream_t st) {
     for (int t = 0; t < bd->ntarget; ++t) { bt.slots[t] = g_tune_stats.p + t * per; pt.bnb_slots[t] = bt.slots[t]; }
     at.bnb_desc = &bt;
   }
-  static const std::vector<int> cands = {-2, 0,  1,  2,  3,  4,  5,  10, 11, 12, 13,
-                                         14, 15, 16, 18, 19, 20, 21, 22, 24, 25, 26};
-  return tune::fastest(cands, -2, st, [&](int c) { return run_candidate(c, at, pt, st); });
+  return tune::fastest(pgemm_tune_candidates(), -2, st, [&](int c) { return run_candidate(c, at, pt, st); });
 }
 
 template <typename T>

@@ -1,6 +1,10 @@
-// Pipelined LDS-DMA implicit-GEMM convolution (bf16, gfx950) — see pgemm.hip.
+// Pipelined LDS-DMA implicit-GEMM convolution (bf16, gfx950): the launch
+// arguments, the candidate ids and each kernel family's launcher.  The kernels:
+// pgemm_tile.h, pstream_kernel.h, conv3x3.hip, pp256.hip, rstream.hip.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <vector>
 
 namespace artsbir {
 
@@ -98,17 +102,91 @@ extern int g_wgrad_cus;
 int pwgrad_num_cfgs();
 int pwgrad_level(int c);
 
-// Launch candidate `cfg` (0..4: tile shapes of the pipelined kernel, 10: the
-// persistent streaming kernel).  Returns false, launching nothing, when the
-// shape is outside what that kernel supports.
+// ---------------------------------------------------------------------------
+// The conv GEMM candidates.  An id names one kernel form for the tuner
+// (tune.h), its table file and ARTSBIR_PGEMM_CFG; this is the one list of them.
+//   0-5   pgemm_kernel (pgemm_tile.h), the tile shapes of kCfgs below, every
+//         epilogue (fused BN-backward ones: pgemm_bnb.hip); 5 has 32-k stages,
+//         C % 64 == 0, tuned only
+//   10    pstream_kernel (pstream.hip), the persistent streaming kernel: plain,
+//         BN-statistics and run-time BN-backward epilogues
+//   11-13 pgemm_kernel tile shapes 1-3 with the epilogue operands prefetched
+//         into registers (PF; pgemm_glb.hip, as 16, 18, 19)
+//   14    pstream_kernel with the compile-time fused BN-backward epilogue
+//   15    pstream_kernel with 32-k stages (plain / BN statistics)
+//   16    pgemm_kernel 128 x 128, 32-k stages, epilogue operands from global
+//         memory (GLB): fused BN-backward, or plain with a residual / gate
+//   17    pstream_kernel on 32-channel blocks (the two-operand fold only)
+//   18    pgemm_kernel 256 x 128 GLB, fused BN-backward kind 3 with one target
+//   19    pgemm_kernel 256 x 128 GLB, plain / statistics / bias-ReLU-residual
+//   20    sconv_kernel (conv3x3.hip): direct 3x3, B fragments from global memory
+//   21    hconv_kernel (conv3x3.hip): halo-tiled direct 3x3
+//   22/23 pp256_kernel (pp256.hip): ping-pong 256 x 256 tile, one tile per
+//         workgroup / persistent over 256 workgroups (C % 32 == 0)
+//   24/25 10 / 15 with the forward-statistics epilogue's stores non-temporal (NT)
+//   26    rstream_kernel (rstream.hip): streaming 1x1 data gradient with a
+//         RES-kind fused BN-backward epilogue (K 64 / 128, C % 256 == 0)
+// A launch with a two-operand reduction (a.x2, the BatchNorm-backward fold)
+// takes 2, 10, 14, 16, 17, 18, 19 and 22 only (pg_fold_launch).  Every launcher
+// returns false, launching nothing, when the shape or epilogue is outside what
+// its kernel supports.
+// ---------------------------------------------------------------------------
 bool pgemm_launch_cfg(const PgArgs& a, int cfg, hipStream_t st);
-// Candidates 22 / 23 (pp256.hip): the ping-pong 256 x 256 tile, one tile per
-// workgroup / persistent over 256 workgroups; false when the shape or epilogue
-// is outside it (C % 32 != 0, LDS-staged operands).
-bool pp256_launch(const PgArgs& a, bool persistent, hipStream_t st);
-// Candidate 26 (rstream.hip): the streaming 1x1 data gradient with a RES-kind
-// fused BN-backward epilogue (K 64 / 128, C % 256 == 0); false outside it
-bool rstream_launch(const PgArgs& a, hipStream_t st);
+// the tuner's candidates in trial order (gemm.hip)
+const std::vector<int>& pgemm_tune_candidates();
+
+// tile shapes of candidates 0-5; factor weighs pgemm_default_cfg's score
+struct PgCfg {
+  int bpx, bch, lds, threads;
+  float factor;
+};
+inline constexpr PgCfg kCfgs[] = {
+    {256, 256, 2 * 256 * 256, 512, 1.00f},          // 0: 256 x 256, 2 stages
+    {256, 128, 3 * (256 + 128) * 128, 512, 0.95f},  // 1: 256 x 128, 3 stages
+    {256, 64, 3 * (256 + 64) * 128, 512, 0.85f},    // 2: 256 x 64, 3 stages
+    {128, 128, 2 * 256 * 128, 256, 0.80f},          // 3: 128 x 128, 2 stages, 4 waves
+    {256, 32, 4 * (256 + 32) * 128, 512, 0.70f},    // 4: 256 x 32, 4 stages
+    {256, 256, 4 * 512 * 64, 512, 0.0f},           // 5: 256 x 256, four 32-k stages (tuned only)
+};
+constexpr int kNumCfg = 6;
+
+// tiles of bpx pixels x bch channels that cover the output
+inline long long pg_ntiles(const PgArgs& a, int bpx, int bch) {
+  return ((a.M + bpx - 1) / bpx) * ((a.Cout + bch - 1) / bch);
+}
+
+// what pgemm_kernel and pstream_kernel take; multi: C < 64 (several taps per 64-k stage)
+inline bool pg_supported(const PgArgs& a, bool& multi) {
+  if (a.Cout % 32 != 0 || a.M <= 0) return false;
+  if (a.C % 64 == 0) multi = false;
+  else if (a.C == 8 || a.C == 16 || a.C == 32) multi = true;
+  else return false;
+  if (a.R * a.S > 32 || a.K % 8 != 0) return false;
+  if ((long long)a.Cout * a.K * 2 > 0x7fffffffLL) return false;
+  const long long HoWo = (long long)a.Ho * a.Wo;
+  if (((256 + HoWo - 1) / HoWo + 2) * a.sN * 2 > 0x7fffffffLL) return false;
+  if (a.M > (1LL << 40)) return false;
+  // segments: every wave's pixels in one segment, a tile in at most two
+  if (a.seg_m > 0 && (a.seg_m % 64 != 0 || a.seg_m < 256 || a.M % a.seg_m != 0)) return false;
+  if (a.bnb && (a.stats || a.Cout % 8 != 0)) return false;
+  return true;
+}
+
+// the launchers of each family, by candidate (multi: pg_supported's)
+bool pg_pf_launch(int c, const PgArgs& a, bool multi, hipStream_t st);                    // 11-13
+bool pg_glb_launch(const PgArgs& a, bool multi, hipStream_t st);                          // 16
+bool pg_glb2_launch(const PgArgs& a, bool multi, hipStream_t st);                         // 18
+bool pg_k32w8_launch(const PgArgs& a, bool multi, hipStream_t st);                        // 19
+bool pg_fold_launch(const PgArgs& a, int c, hipStream_t st);                              // a.x2 set
+bool pstream_plain_launch(const PgArgs& a, bool multi, hipStream_t st);                   // 10
+bool pstream_bnb_launch(const PgArgs& a, bool multi, hipStream_t st);                     // 14
+bool pstream_k32_launch(const PgArgs& a, bool multi, hipStream_t st);                     // 15
+bool pstream_fold_launch(const PgArgs& a, int c, hipStream_t st);                         // 10 / 14 / 17, a.x2 set
+bool sconv_launch(const PgArgs& a, hipStream_t st);                                       // 20
+bool sconv_ok(const PgArgs& a);  // the shapes sconv_launch takes
+bool hconv_launch(const PgArgs& a, hipStream_t st);                                       // 21
+bool pp256_launch(const PgArgs& a, bool persistent, hipStream_t st);                      // 22 / 23
+bool rstream_launch(const PgArgs& a, hipStream_t st);                                     // 26
 // whether a launch with a two-operand reduction / per-segment weights can be
 // taken by a tile of BPX pixels (1x1 only, C1 a whole number of KS-k stages,
 // segments a whole number of tiles)

@@ -1,7 +1,9 @@
-// Device-side building blocks of the pipelined implicit-GEMM kernels (pgemm.hip,
-// pp256.hip): LDS-DMA loads, counted waits, XCD remap, the channel permutation
-// of the weight tile, BN statistics / fused BN-backward epilogues.  Header-only
-// (inline device functions and templates), shared by both translation units.
+// Device-side building blocks of the pipelined implicit-GEMM kernels
+// (pgemm_tile.h, pstream.hip, conv3x3.hip, pp256.hip, pw256.hip, rstream.hip,
+// bstream.hip): LDS-DMA loads, counted waits, XCD remap, the channel
+// permutation of the weight tile, BN statistics / fused BN-backward epilogues.
+// Header-only (inline device functions and templates), shared by every unit
+// that holds one of those kernels.
 #pragma once
 #include "common.h"
 #include "pgemm.h"
@@ -9,21 +11,17 @@
 namespace artsbir {
 
 #define PG_OOB 0x80000000u
-#ifndef PG_SNAKE
-#define PG_SNAKE 1  // GLB epilogue: odd channel pairs walk the pixel tiles backwards (pg_epilogue_k)
-#endif
-#ifndef PG_PRIO
-#define PG_PRIO 1
-#endif
-#if PG_PRIO
+// GLB epilogue: odd channel pairs walk the pixel tiles backwards (pg_epilogue_k)
+constexpr bool kPgSnake = true;
+// the global-operand (GLB) epilogues store their output non-temporally: the
+// lines are not allocated in L2, so the residual / BN-target operand lines the
+// next channel pair reads stay resident (read bytes -15 %, C2 step -0.6 to
+// -0.8 ms; tools/gpu/r4_ntst.sh, r4_ntst_step.sh, profiles/r4_nt_stores.txt)
+constexpr bool kPgNtStore = true;
 // raise wave priority around each MFMA cluster (guide T5: keeps hipcc from
 // spreading the cluster across the stage barriers)
 #define PG_PRIO_ON() __builtin_amdgcn_s_setprio(1)
 #define PG_PRIO_OFF() __builtin_amdgcn_s_setprio(0)
-#else
-#define PG_PRIO_ON()
-#define PG_PRIO_OFF()
-#endif
 typedef __attribute__((address_space(3))) void* pg_lds_t;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4v;
 
@@ -600,7 +598,8 @@ __device__ __forceinline__ void pg_epilogue_k(const PgArgs& a, const f32x4 (&acc
   const bool sums = BNB || a.stats != nullptr;
   const bool res = RESK || (BK == 0 && a.res_mode != 0);
   const float rsc = a.res_mode == 2 ? 0.25f : 1.f;
-  static_assert(!PFN || (BK == 0 && !REG && EJB >= NTP), "PFN: plain epilogue, one batch per pair");
+  // (EJB == NTP makes the batch below, EJ, the pair's NTP pixel tiles: pfn_next[] holds exactly one batch)
+  static_assert(!PFN || (BK == 0 && !REG && EJB == NTP), "PFN: plain epilogue, one batch per pair");
   // PFN: the residual / gate operand rows of pair pp (the loads of the u loop below)
   auto pfn_load = [&](int pp, Vec16<bf16> (&dst)[NTP]) {
     const int c0 = bch + wch * WTCH + 32 * pp + 8 * fq;
@@ -659,7 +658,7 @@ __device__ __forceinline__ void pg_epilogue_k(const PgArgs& a, const f32x4 (&acc
     for (int jj = 0; jj < NTP; jj += EJ) {
       // GLB: odd channel pairs walk the pixel tiles backwards, so the lines whose
       // first 64-B half the previous pair read last are re-read first (still in L2)
-      const int j0 = (GLB && PG_SNAKE && (p & 1)) ? NTP - EJ - jj : jj;
+      const int j0 = (GLB && kPgSnake && (p & 1)) ? NTP - EJ - jj : jj;
       Vec16<bf16> rv[EJ], y0v[EJ], mkv[EJ], y1v[EJ];
       unsigned mbits[EJ];
       if constexpr (PFN) {
@@ -771,14 +770,7 @@ __device__ __forceinline__ void pg_epilogue_k(const PgArgs& a, const f32x4 (&acc
           Vec16<bf16> o;
 #pragma unroll
           for (int e = 0; e < 8; ++e) o.v[e] = from_f<bf16>(v[e]);
-#ifndef PG_NT_STORE
-// the global-operand (GLB) epilogues store their output non-temporally: the
-// lines are not allocated in L2, so the residual / BN-target operand lines the
-// next channel pair reads stay resident (read bytes -15 %, C2 step -0.6 to
-// -0.8 ms; tools/gpu/r4_ntst.sh, r4_ntst_step.sh, profiles/r4_nt_stores.txt)
-#define PG_NT_STORE 1
-#endif
-          if (PG_NT_STORE && GLB) {
+          if (kPgNtStore && GLB) {
             typedef __attribute__((ext_vector_type(4))) unsigned pg_u4;
             __builtin_nontemporal_store(*reinterpret_cast<const pg_u4*>(&o),
                                         reinterpret_cast<pg_u4*>(reinterpret_cast<bf16*>(a.y) + px * a.ldy + ch0));
