@@ -178,8 +178,6 @@ SIGNATURES = {
     "artsbir_adam_step": [_vp, _vp, _c_ll, _c_ll, _c_float, _c_float, _c_float, _c_float, _c_float, _c_ll, _vp],
     "artsbir_pairwise_l2": [_vp, _c_ll, _vp, _c_ll, _c_int, _c_float, _vp, _vp],
     "artsbir_rows_prep": [_c_int, _vp, _c_int, _c_int, _vp, _vp, _c_int, _vp],
-    "artsbir_knn_band": [_vp, _vp, _vp, _c_ll, _c_ll, _vp, _c_float, _c_int, _c_int, _c_float, _vp, _vp, _vp, _vp],
-    "artsbir_knn_band_from_dpos": [_vp, _vp, _c_float, _c_int, _c_float, _vp, _vp, _vp],
     "artsbir_knn_candidates_per_query": [_c_int, _c_int],
     "artsbir_knn_scan": [_c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int,
                          _vp, _vp, _vp],
@@ -187,10 +185,6 @@ SIGNATURES = {
     "artsbir_knn_scan_aug_supported": [_c_int],
     "artsbir_knn_scan_aug": [_vp, _vp, _vp, _c_float, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_float,
                              _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _vp],
-    "artsbir_knn_merge": [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_float, _c_float, _c_ll, _c_int, _vp,
-                          _vp, _vp, _vp],
-    "artsbir_knn_uncertain": [_vp, _vp, _c_int, _vp, _c_int, _vp, _vp, _c_ll, _vp, _vp],
-    "artsbir_knn_exact_all": [_vp, _vp, _c_int, _c_int, _vp, _vp],
     "artsbir_pairwise_l2_topk_workspace": [_c_int, _c_int, _c_ll, _c_int, _c_int, _c_int],
     "artsbir_pairwise_l2_topk": [_c_int, _c_int, _vp, _c_int, _vp, _c_ll, _c_int, _c_int, _vp, _vp, _c_ll, _c_int,
                                  _vp, _vp, _vp, _vp, _vp, _c_ll, _vp],

@@ -7,20 +7,39 @@
 // exact: distances are EVALUATED in f64 from the f32 features and sorted by
 // (distance, gallery index) — the oracle's definition (oracle/retrieval.py).
 //
-//  1. knn_scan_kernel (MFMA): for a (query tile x gallery chunk) workgroup,
-//     stream gallery tiles, compute approximate squared distances
-//     |q|^2 + |g|^2 - 2 q.g with bf16 (or exact-f32) MFMA and
-//       * keep, per query, the T smallest approximate values of the chunk
-//         (threshold filter -> rare insertions into a per-query register list),
-//       * count items certainly closer than the positive (approx < lo_q) and
-//         queue the uncertain ones (lo_q <= approx <= hi_q) for exact checks,
-//     where [lo_q, hi_q] = d_pos^2 -/+ eps_q and eps_q bounds the approximation
-//     error of the squared distance;
-//  2. knn_merge_kernel: exact f64 distances of the S*T candidates of a query,
-//     top-k by (distance, index), plus a verification flag if a chunk list
-//     could have dropped a true top-k item (then the host reruns that query
-//     with an exhaustive exact scan);
-//  3. knn_uncertain_kernel: exact checks of the queued uncertain items.
+//
+// artsbir_pairwise_l2_topk is one call: it launches the stages below in this
+// order on the caller's stream and never synchronises with the host; what used
+// to be a host decision (max |g|^2, a queue overflow, a query to rerun) is made
+// on the device.  The file follows the same order.
+//   prep      f32 |x|^2 of every row and its copy in the compute dtype (unit rows
+//             for the cosine metric); the gallery's min / max |g|^2.
+//   band      per query eps_q, the bound of the approximation error of a squared
+//             distance, and [lo_q, hi_q] = d_pos^2 -/+ eps_q from the exact key of
+//             the positive.
+//   scan      (query tile x gallery chunk) workgroups stream the chunk's gallery
+//             tiles and compute approximate squared distances |q|^2 + |g|^2 - 2 q.g
+//             by MFMA: knn_scan_v2_kernel (bf16, padded D in {64, 128, 256, 512})
+//             or knn_scan_kernel (v1: bf16 at any other width, exact-f32 MFMA).
+//             Per (query, chunk) they keep the KT = 16 smallest approximate values
+//             (threshold filter -> rare insertions into a register list), count
+//             the items certainly closer than the positive (approx < lo_q) and
+//             queue the uncertain ones (lo_q <= approx <= hi_q).
+//   merge     k <= 64: one wave per query takes the exact f64 keys of the listed
+//             candidates that can still reach the top k and the k smallest by
+//             (key, index); it flags the query if a chunk list could have dropped
+//             a true top-k item.
+//   rank      exact checks of the queued uncertain items; if the queue overflowed,
+//             every rank is recounted exhaustively.
+//   large k   65 <= k <= 1024: the lists give a per-query cut instead, a second
+//             scan pass in collect mode gathers every row under it, and one
+//             workgroup per query sorts their exact keys; a query whose buffer
+//             overflowed is flagged.
+//   fallbacks flagged queries get an exhaustive exact top-k.  Both fallback
+//             chains always launch and return at once when nothing is flagged.
+// After them come the plan (chunking and workspace layout), the call itself and
+// the small entry points that expose single stages to tests, tools and the
+// sharded path.
 //
 // Error bound of the approximate squared distance |q|^2 + |g|^2 - 2 q.g
 // (norms in f32 from the f32 rows, the dot product from the compute copies):
@@ -68,7 +87,56 @@ template <> struct RM<float> {
   }
 };
 
-// ---------------------------------------------------------------- helpers
+// ------------------------------------------ exact keys (used by every stage)
+// exact ||q - g + eps|| in f64 (one wave)
+__device__ __forceinline__ double exact_l2(const float* q, const float* g, int D, int lane) {
+  double s = 0.0;
+  for (int d = lane; d < D; d += 64) {
+    const double t = ((double)q[d] - (double)g[d]) + 1e-6;
+    s += t * t;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  return sqrt(s);
+}
+
+// Exact ordering key of (q, g) in f64 (one wave; all lanes return it):
+//   metric 0  ||q - g + 1e-6||                                 nn.PairwiseDistance(p=2, eps=1e-6), utils.py:42
+//   metric 1  1 - q.g / (max(|q|, 1e-8) max(|g|, 1e-8))        cosine_distance, utils.py:31-40
+//             (nn.CosineSimilarity(dim=1, eps=1e-8): each norm clamped separately)
+__device__ __forceinline__ double exact_key(const float* q, const float* g, int D, int lane, int metric) {
+  if (metric == 0) return exact_l2(q, g, D, lane);
+  double dot = 0.0, qq = 0.0, gg = 0.0;
+  for (int d = lane; d < D; d += 64) {
+    const double a = q[d], b = g[d];
+    dot += a * b;
+    qq += a * a;
+    gg += b * b;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    dot += __shfl_xor(dot, o, 64);
+    qq += __shfl_xor(qq, o, 64);
+    gg += __shfl_xor(gg, o, 64);
+  }
+  return 1.0 - dot / (fmax(sqrt(qq), 1e-8) * fmax(sqrt(gg), 1e-8));
+}
+
+// the scan-domain squared distance of an exact key: d^2 itself for L2; for the
+// cosine metric the scan runs on unit rows where d^2 = 2 key (the deviation of
+// the f32 unit rows' norms from 1 is folded into the per-query eps, knn_qeps)
+__device__ __forceinline__ double key_d2(double key, int metric) { return metric ? 2.0 * key : key * key; }
+
+// per-query bound of |approx d^2 - scan-domain exact d^2|: rel |q| max|g| + 1e-3,
+// plus for the cosine metric 2 (|1 - |q|^2| + max(gmax - 1, 1 - gmin)), the room
+// between 2 key and |q^|^2 + |g^|^2 - 2 q^.g^ of the normalised f32 rows
+__device__ __forceinline__ double query_eps(float qsq, float gmax, float gmin, float rel, int metric) {
+  double e = rel * sqrt((double)qsq * gmax) + 1e-3;
+  if (metric) e += 2.0 * (fabs(1.0 - (double)qsq) + fmax((double)gmax - 1.0, 1.0 - (double)gmin));
+  return e;
+}
+
+// ------------------------------------------------------------------- prep
 // squared norm of each f32 row, and the compute-dtype copy of the row.
 // normalize (cosine metric): the row is first scaled by 1/max(|x|, 1e-8) (|x| in
 // f64), so the L2 scan of the unit rows orders by 1 - cos (|a-b|^2 = 2 - 2 cos)
@@ -131,64 +199,110 @@ __global__ void rows_prep_kernel(const float* __restrict__ x, int n, int D, floa
   if (lane == 0) sq[row] = s;
 }
 
-// exact ||q - g + eps|| in f64 (one wave)
-__device__ __forceinline__ double exact_l2(const float* q, const float* g, int D, int lane) {
-  double s = 0.0;
-  for (int d = lane; d < D; d += 64) {
-    const double t = ((double)q[d] - (double)g[d]) + 1e-6;
-    s += t * t;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  return sqrt(s);
+// one wave per row, the copy in the compute dtype
+static void launch_rows_prep(int dtype, const float* x, int n, int D, float* sq, void* xc, int ldc, int normalize,
+                             hipStream_t st) {
+  const dim3 g((unsigned)((n + 3LL) / 4));
+  if (dtype == ARTSBIR_DT_BF16)
+    hipLaunchKernelGGL(rows_prep_kernel<bf16>, g, dim3(256), 0, st, x, n, D, sq, (bf16*)xc, ldc, normalize);
+  else
+    hipLaunchKernelGGL(rows_prep_kernel<float>, g, dim3(256), 0, st, x, n, D, sq, (float*)xc, ldc, normalize);
 }
 
-// Exact ordering key of (q, g) in f64 (one wave; all lanes return it):
-//   metric 0  ||q - g + 1e-6||                                 nn.PairwiseDistance(p=2, eps=1e-6), utils.py:42
-//   metric 1  1 - q.g / (max(|q|, 1e-8) max(|g|, 1e-8))        cosine_distance, utils.py:31-40
-//             (nn.CosineSimilarity(dim=1, eps=1e-8): each norm clamped separately)
-__device__ __forceinline__ double exact_key(const float* q, const float* g, int D, int lane, int metric) {
-  if (metric == 0) return exact_l2(q, g, D, lane);
-  double dot = 0.0, qq = 0.0, gg = 0.0;
-  for (int d = lane; d < D; d += 64) {
-    const double a = q[d], b = g[d];
-    dot += a * b;
-    qq += a * a;
-    gg += b * b;
+// augmented bf16 rows for knn_scan_v2: [n][Dp + 8], columns Dp..Dp+1 = f32 |x|^2
+// (normalize: unit rows for the cosine metric, as rows_prep_kernel)
+__global__ void rows_prep_aug_kernel(const float* __restrict__ x, int n, int D, int Dp, float* __restrict__ sq,
+                                     bf16* __restrict__ xa, int normalize) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+  if (row >= n) return;
+  const float* r = x + (long long)row * D;
+  const float sc = row_scale(r, D, lane, normalize);
+  bf16* o = xa + (long long)row * (Dp + 8);
+  float s = 0.f;
+  if (row_vec_ok(r, D)) {
+    // 8 consecutive columns per lane: two 16-B loads, one 16-B store of the
+    // bf16 copy (the row pitch 2 (Dp + 8) B is a multiple of 16)
+    for (int d0 = lane * 8; d0 < Dp; d0 += 512) {
+      float v[8];
+      row_load8(r, D, d0, sc, v);
+      bf16 h[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        s = fmaf(v[j], v[j], s);  // explicit fma: the same rounding in both kernels
+        h[j] = (bf16)v[j];
+      }
+      *reinterpret_cast<uint4*>(o + d0) = *reinterpret_cast<const uint4*>(h);
+    }
+  } else {
+    for (int d = lane; d < Dp; d += 64) {
+      const float v = d < D ? r[d] * sc : 0.f;
+      s = fmaf(v, v, s);
+      o[d] = (bf16)v;
+    }
+  }
+  s = warp_sum(s);
+  if (lane < 8) {
+    const unsigned bits = __float_as_uint(s);
+    unsigned short v = 0;
+    if (lane == 0) v = (unsigned short)(bits & 0xffffu);
+    if (lane == 1) v = (unsigned short)(bits >> 16);
+    reinterpret_cast<unsigned short*>(o)[Dp + lane] = v;
+  }
+  if (lane == 0) sq[row] = s;
+}
+
+// min and max of |g|^2 over the gallery into ext[0] (max), ext[1] (min) as f32
+// bit patterns (non-negative floats order like their bits); ext preset to (0, +INF)
+__global__ void sq_minmax_kernel(const float* __restrict__ sq, long long n, unsigned* __restrict__ ext) {
+  float mx = 0.f, mn = INFINITY;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    mx = fmaxf(mx, sq[i]);
+    mn = fminf(mn, sq[i]);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    dot += __shfl_xor(dot, o, 64);
-    qq += __shfl_xor(qq, o, 64);
-    gg += __shfl_xor(gg, o, 64);
+    mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    mn = fminf(mn, __shfl_xor(mn, o, 64));
   }
-  return 1.0 - dot / (fmax(sqrt(qq), 1e-8) * fmax(sqrt(gg), 1e-8));
+  // one atomic pair per workgroup (the atomics on two words serialise: one pair
+  // per wave of a 1024-workgroup grid took ~95 us)
+  __shared__ float smx[16], smn[16];
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { smx[w] = mx; smn[w] = mn; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) { mx = fmaxf(mx, smx[i]); mn = fminf(mn, smn[i]); }
+    atomicMax(ext, __float_as_uint(mx));
+    atomicMin(ext + 1, __float_as_uint(mn));
+  }
 }
 
-// the scan-domain squared distance of an exact key: d^2 itself for L2; for the
-// cosine metric the scan runs on unit rows where d^2 = 2 key (the deviation of
-// the f32 unit rows' norms from 1 is folded into the per-query eps, knn_qeps)
-__device__ __forceinline__ double key_d2(double key, int metric) { return metric ? 2.0 * key : key * key; }
-
-// per-query bound of |approx d^2 - scan-domain exact d^2|: rel |q| max|g| + 1e-3,
-// plus for the cosine metric 2 (|1 - |q|^2| + max(gmax - 1, 1 - gmin)), the room
-// between 2 key and |q^|^2 + |g^|^2 - 2 q^.g^ of the normalised f32 rows
-__device__ __forceinline__ double query_eps(float qsq, float gmax, float gmin, float rel, int metric) {
-  double e = rel * sqrt((double)qsq * gmax) + 1e-3;
-  if (metric) e += 2.0 * (fabs(1.0 - (double)qsq) + fmax((double)gmax - 1.0, 1.0 - (double)gmin));
-  return e;
+// ------------------------------------------------------------------- band
+// per-query eps (query_eps) and the initial dpos (caller's value for shard
+// calls, else -1); cnt and the uncertain-queue length start at 0
+__global__ void knn_init_kernel(const float* __restrict__ qsq, const unsigned* __restrict__ ext, int nq, float rel,
+                                int metric, const double* __restrict__ dpos_in, float* __restrict__ qeps,
+                                double* __restrict__ dpos, int* __restrict__ cnt, int* __restrict__ unc_n) {
+  const int qi = blockIdx.x * blockDim.x + threadIdx.x;
+  if (qi == 0) *unc_n = 0;
+  if (qi >= nq) return;
+  const float gmax = __uint_as_float(ext[0]), gmin = __uint_as_float(ext[1]);
+  qeps[qi] = (float)(query_eps(qsq[qi], gmax, gmin, rel, metric) * (1.0 + 1e-6));
+  dpos[qi] = dpos_in ? dpos_in[qi] : -1.0;
+  cnt[qi] = 0;
 }
 
-// d_pos^2 (exact, f64) and the uncertainty band of every query
+// d_pos^2 (exact, f64) and the uncertainty band of every query, eps from knn_init_kernel
 __global__ void knn_band_kernel(const float* __restrict__ q, const float* __restrict__ g, const long long* __restrict__ pos,
-                                long long g_base, long long n_g, const float* __restrict__ qsq, float gsq_max, int nq, int D,
-                                float rel, double* __restrict__ dpos, float* __restrict__ lo, float* __restrict__ hi,
-                                int metric, const float* __restrict__ qeps) {
+                                long long g_base, long long n_g, int nq, int D, double* __restrict__ dpos,
+                                float* __restrict__ lo, float* __restrict__ hi, int metric,
+                                const float* __restrict__ qeps) {
   const int lane = threadIdx.x & 63;
   const int qi = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
   if (qi >= nq) return;
   const long long p = pos[qi];
-  const double eps = qeps ? (double)qeps[qi] : rel * sqrt((double)qsq[qi] * gsq_max) + 1e-3;
+  const double eps = qeps[qi];
   if (p < g_base || p >= g_base + n_g) {
     // positive not in this shard: the caller provides dpos from its owner
     if (lane == 0) {
@@ -206,47 +320,47 @@ __global__ void knn_band_kernel(const float* __restrict__ q, const float* __rest
   }
 }
 
-__global__ void knn_band_from_dpos_kernel(const double* __restrict__ dpos, const float* __restrict__ qsq, float gsq_max,
-                                          int nq, float rel, float* __restrict__ lo, float* __restrict__ hi) {
-  const int qi = blockIdx.x * blockDim.x + threadIdx.x;
-  if (qi >= nq) return;
-  const double eps = rel * sqrt((double)qsq[qi] * gsq_max) + 1e-3;
-  const double d = dpos[qi];
-  lo[qi] = d >= 0 ? (float)(d * d - eps) : -1.f;
-  hi[qi] = d >= 0 ? (float)(d * d + eps) : -1.f;
-}
-
-// ------------------------------------------------------------ fused scan
+// ------------------------------- v1 scan (bf16 or f32 MFMA from LDS tiles)
+// The arguments of both scans.  The defaults are "not used"; a call site names
+// what it uses.
 struct KnnScanArgs {
-  const void* q;  // [Nq][D] compute dtype
-  const void* g;  // [Ng][D] compute dtype
-  const float* qsq;
-  const float* gsq;
-  float gsq_max;  // knn_scan_v2: max |g|^2 (prefilter slack)
-  const float* gsq_max_p;  // knn_scan_v2: if set, max |g|^2 read from device memory (one-call path, no host sync)
-  const float* thr0;  // knn_scan_v2: optional per-query initial list threshold (see knn.py)
-  unsigned* kb;       // knn_scan_v2: optional [Nq] shared k-th bound (kb_enc of an approx d2), atomicMin
-  unsigned* hist;     // knn_scan_v2 (with kb): optional [Nq][HB_BINS] counts of published list items (zeroed)
-  unsigned* hbase;    //   [Nq] the histogram's first bin key (0: not chosen yet; zeroed)
-  int kq;             //   k of the final top-k (1..KT)
-  float rel;          //   error bound factor of the approximate d2 (eps = rel |q| max|g| + 1e-3)
-  int Nq, Ng, D;
-  int tiles_per_chunk;
-  int nchunks;
-  const float* lo;  // rank band (nullptr: no rank)
-  const float* hi;
-  int* cnt;         // [Nq] items certainly closer than the positive
-  int* unc;         // [unc_cap][2] (query, local gallery index); unc_n = unc + 2*unc_cap
-  int unc_cap;
-  float* cand_d;    // [Nq][nchunks][KT]
-  int* cand_i;
+  const void* q = nullptr;  // [Nq][D] compute dtype
+  const void* g = nullptr;  // [Ng][D] compute dtype (knn_scan_v2: the augmented rows)
+  const float* qsq = nullptr;
+  const float* gsq = nullptr;
+  float gsq_max = 0.f;  // knn_scan_v2: max |g|^2 (prefilter slack)
+  const float* gsq_max_p = nullptr;  // knn_scan_v2: if set, max |g|^2 read from device memory (one-call path, no host sync)
+  const float* thr0 = nullptr;  // knn_scan_v2: optional per-query initial list threshold (see knn.py)
+  unsigned* kb = nullptr;       // knn_scan_v2: optional [Nq] shared k-th bound (kb_enc of an approx d2), atomicMin
+  unsigned* hist = nullptr;     // knn_scan_v2 (with kb): optional [Nq][HB_BINS] counts of published list items (zeroed)
+  unsigned* hbase = nullptr;    //   [Nq] the histogram's first bin key (0: not chosen yet; zeroed)
+  int kq = 0;                   //   k of the final top-k (1..KT)
+  float rel = 0.f;              //   error bound factor of the approximate d2 (eps = rel |q| max|g| + 1e-3)
+  int Nq = 0, Ng = 0, D = 0;
+  int tiles_per_chunk = 0;
+  int nchunks = 0;
+  const float* lo = nullptr;  // rank band (nullptr: no rank)
+  const float* hi = nullptr;
+  int* cnt = nullptr;         // [Nq] items certainly closer than the positive
+  int* unc = nullptr;         // [unc_cap][2] (query, local gallery index); unc_n = unc + 2*unc_cap
+  int unc_cap = 0;
+  float* cand_d = nullptr;    // [Nq][nchunks][KT]
+  int* cand_i = nullptr;
   // collect mode (template parameter CM of the scans, the large-k path): every row
   // with approximate d2 under the query's thr0 is appended to col_i[q][col_cap]
   // through the counter col_n[q] (which keeps counting past col_cap)
-  int* col_n;
-  int* col_i;
-  int col_cap;
+  int* col_n = nullptr;
+  int* col_i = nullptr;
+  int col_cap = 0;
+
+  // the gallery in chunks of tiles_per_chunk tiles of 128 rows (both scans)
+  void chunks(int ng, int tpc) {
+    Ng = ng;
+    tiles_per_chunk = tpc;
+    nchunks = ((ng + 127) / 128 + tpc - 1) / tpc;
+  }
 };
+static_assert(sizeof(KnnScanArgs) == 192 && offsetof(KnnScanArgs, col_cap) == 184, "a kernel argument: the layout is fixed");
 
 constexpr int KT = 16;  // per (query, chunk) candidate list length
 
@@ -451,7 +565,17 @@ __global__ void __launch_bounds__(256) knn_scan_kernel(KnnScanArgs a) {
   }
 }
 
-// ------------------------------------- register-resident scan (bf16, v2)
+// one workgroup per (128-query tile, gallery chunk)
+template <int CM>
+static void launch_scan_v1(int dtype, const KnnScanArgs& a, hipStream_t st) {
+  const dim3 g((unsigned)(a.nchunks * ((a.Nq + 127) / 128)));
+  if (dtype == ARTSBIR_DT_BF16)
+    hipLaunchKernelGGL((knn_scan_kernel<bf16, CM>), g, dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((knn_scan_kernel<float, CM>), g, dim3(256), 0, st, a);
+}
+
+// ------------------------------ v2 scan (bf16, queries resident in registers)
 // One workgroup = 8 waves = 256 queries x one gallery chunk.  Each wave holds
 // the MFMA A fragments of its 32 queries over the whole of D in registers
 // (KB = Dp/16 uint4 per lane) and streams the chunk in 32-row gallery tiles
@@ -500,6 +624,7 @@ template <int N>
 __device__ __forceinline__ void rvm_wait() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
+// n = the DMAs of one tile a wave issues: 0 .. 5 (V2<KB>::NI = KB + 1 <= 33 pieces over 8 waves)
 __device__ __forceinline__ void rvm_wait_n(int n) {
   switch (n) {
     case 1: rvm_wait<1>(); break;
@@ -507,11 +632,6 @@ __device__ __forceinline__ void rvm_wait_n(int n) {
     case 3: rvm_wait<3>(); break;
     case 4: rvm_wait<4>(); break;
     case 5: rvm_wait<5>(); break;
-    case 6: rvm_wait<6>(); break;
-    case 7: rvm_wait<7>(); break;
-    case 8: rvm_wait<8>(); break;
-    case 9: rvm_wait<9>(); break;
-    case 10: rvm_wait<10>(); break;
     default: rvm_wait<0>(); break;
   }
 }
@@ -570,11 +690,15 @@ __device__ float hb_bound(const unsigned* hq, unsigned base, int kq) {
 constexpr int V2_ROWS = 32;  // gallery rows per tile
 // tiles between two exchanges of the shared per-query bound (power of two; env
 // ARTSBIR_KNN_KB=0 turns the exchange off in the one-call path)
-#ifndef KB_SYNC_TILES
-#define KB_SYNC_TILES 128  // round 5, after the prefetch fix: 32 / 64 / 128 -> 11.44 / 11.20 / 11.14 ms (profiles/r5_knn_kb.txt)
-#endif
-constexpr int KB_SYNC = KB_SYNC_TILES;
-constexpr int V2_WAVES = 8;  // 8 x 32 = 256 queries per workgroup
+constexpr int KB_SYNC = 128;  // round 5, after the prefetch fix: 32 / 64 / 128 -> 11.44 / 11.20 / 11.14 ms (profiles/r5_knn_kb.txt)
+// 8 waves x 32 queries = 256 queries per workgroup, two waves per SIMD.  4 waves
+// of 64 (one per SIMD, each B fragment feeding two MFMAs) were exact but 30 %
+// slower (profiles/r6_knn_qh.txt)
+constexpr int V2_WAVES = 8;
+// B fragments read ahead of their MFMA in the tile loop.  At 6 the kernel needs
+// 256 VGPRs plus a 16-B spill whose reload before the first MFMA of every tile
+// carried s_waitcnt vmcnt(0), draining the DMA ring each tile; 4 spills nothing
+constexpr int KNN_PF = 4;
 
 template <int KB>
 struct V2 {
@@ -582,24 +706,17 @@ struct V2 {
   static constexpr int SLOTS = V2_ROWS * RB / 16;       // 16-B slots per tile
   static constexpr int NI = (SLOTS + 63) / 64;          // DMA instructions per tile
   static constexpr int STAGE = NI * 1024;
-  // KNN_NST 4: three tiles in flight instead of two; the LDS it takes comes
-  // from the slow path's staging, which then holds half a wave's rows per pass.
-  // Measured slower again once the per-tile drain was gone (scan 11.2 -> 12.0 ms,
-  // profiles/r5_knn_nst4.txt; round 4's 4-stage build ran under that drain), so
-  // the DMA ring's depth does not bound the scan: 3 stays
-#ifndef KNN_NST
-#define KNN_NST 3
-#endif
-  static constexpr int NST = KNN_NST;
-  static constexpr int SROWS = NST == 4 ? 16 : 32;       // staged rows per slow-path pass
+  // ring stages: two tiles in flight.  A 4-stage ring (its LDS taken from the slow
+  // path's staging) was slower, 11.2 -> 12.0 ms (profiles/r5_knn_nst4.txt): the
+  // ring's depth does not bound the scan
+  static constexpr int NST = 3;
   static constexpr int SP = 33;                          // staging pitch (floats)
-  static constexpr int WSTG = SROWS * SP + (SROWS == 32 ? 0 : 32);  // + the 32 columns' |g|^2 (in the row padding at 32 rows)
+  static constexpr int WSTG = 32 * SP;                   // a wave's 32 staged rows; the 32 columns' |g|^2 in the row padding
   static constexpr int STG = V2_WAVES * WSTG * 4;
   static constexpr int ROWS = V2_WAVES * 32;
   static constexpr int LDS = NST * STAGE + STG + 5 * ROWS * 4;
   static_assert(LDS <= 163840, "LDS");
   static_assert((NI + V2_WAVES - 1) / V2_WAVES <= 5, "rvm_wait_n covers at most 5 DMA per wave");
-  static_assert((NI + V2_WAVES / 2 - 1) / (V2_WAVES / 2) <= 10, "rvm_wait_n covers at most 10 DMA per wave");
 };
 
 // scan statistics (diagnostics, ARTSBIR_KNN_STAT=1): wave-tiles, slow-path
@@ -611,19 +728,13 @@ static bool knn_stat_on() {
   return on;
 }
 
-// QH: query halves per wave.  1: 8 waves of 32 queries (two waves per SIMD);
-// 2: 4 waves of 64 (one wave per SIMD, the A fragments of both halves resident:
-// 2 KB registers per lane at D = 512, AGPRs included), so each B fragment read
-// from LDS feeds two MFMAs — half the LDS reads per MAC — and every lane owns a
-// query row in the list / slow path (ARTSBIR_KNN_QH, knn_qh())
 // CM 1 (collect mode, the large-k path): thr0 is the query's fixed cut; a row under
 // it is appended to the query's candidate buffer instead of entering the list, and
 // no list is written
-template <int KB, int QH = 1, int CM = 0>
-__global__ void __launch_bounds__(64 * V2_WAVES / QH, 1) knn_scan_v2_kernel(KnnScanArgs a, int stat) {
+template <int KB, int CM = 0>
+__global__ void __launch_bounds__(64 * V2_WAVES, 1) knn_scan_v2_kernel(KnnScanArgs a, int stat) {
   using C = V2<KB>;
-  constexpr int NWV = V2_WAVES / QH;  // waves of the workgroup
-  static_assert(QH == 1 || (QH == 2 && C::SROWS == 32), "QH 2: the 3-stage ring (full-tile staging)");
+  constexpr int NWV = V2_WAVES;  // waves of the workgroup
   __shared__ __attribute__((aligned(16))) char smem[C::LDS];
   float* s_stage = reinterpret_cast<float*>(smem + C::NST * C::STAGE);
   float* s_thr = s_stage + V2_WAVES * C::WSTG;     // [256] 16th smallest so far (-INF: row unused)
@@ -654,12 +765,9 @@ __global__ void __launch_bounds__(64 * V2_WAVES / QH, 1) knn_scan_v2_kernel(KnnS
   const __amdgpu_buffer_rsrc_t gr =
       rrsrc(reinterpret_cast<const char*>(a.g) + (long long)g0 * C::RB, (long long)(a.Ng - g0) * C::RB);
   // a tile is NI (33 at D = 512) 1-KB pieces over 8 waves: the wave issuing
-  // the odd piece rotates with the tile (KNN_ROT), so no wave is the one every
-  // barrier waits for
-#ifndef KNN_ROT
-#define KNN_ROT 1
-#endif
-  auto w_of = [&](int t) { return KNN_ROT ? (wid + t) & (NWV - 1) : wid; };
+  // the odd piece rotates with the tile, so no wave is the one every barrier
+  // waits for
+  auto w_of = [&](int t) { return (wid + t) & (NWV - 1); };
   auto ni_of = [&](int t) { const int w2 = w_of(t); return w2 < C::NI ? (C::NI - w2 + NWV - 1) / NWV : 0; };
   auto issue_tile = [&](int t) {
     char* st = smem + (t % C::NST) * C::STAGE;
@@ -668,7 +776,6 @@ __global__ void __launch_bounds__(64 * V2_WAVES / QH, 1) knn_scan_v2_kernel(KnnS
   };
   issue_tile(0);
   if (ntiles > 1) issue_tile(1);
-  if (C::NST == 4 && ntiles > 2) issue_tile(2);
 
   const float* band_lo = a.lo;
   const float* band_hi = a.hi;
@@ -686,19 +793,15 @@ __global__ void __launch_bounds__(64 * V2_WAVES / QH, 1) knn_scan_v2_kernel(KnnS
   const int r32 = lane & 31, h = lane >> 5;
   const __amdgpu_buffer_rsrc_t qr = rrsrc(reinterpret_cast<const bf16*>(a.q) + (long long)qb * (16 * KB),
                                           (long long)(a.Nq - qb) * (32 * KB));
-  uint4 af[QH][KB];
+  uint4 af[KB];
 #pragma unroll
-  for (int qh = 0; qh < QH; ++qh)
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb)
-      af[qh][kb] = rload(qr, (unsigned)(((wid * 32 * QH + qh * 32 + r32) * 16 * KB + kb * 16 + 8 * h) * 2));
-  // owner state: lane r < 32 owns row r of the wave (QH 2: lane l owns row l,
-  // half l >> 5), with its e and accumulator half in the 32x32 accumulator
-  const bool owner = QH == 2 || lane < 32;
-  const int ohalf = QH == 2 ? lane >> 5 : 0;
+  for (int kb = 0; kb < KB; ++kb) af[kb] = rload(qr, (unsigned)(((wid * 32 + r32) * 16 * KB + kb * 16 + 8 * h) * 2));
+  // owner state: lane r < 32 owns row r of the wave, with its e and accumulator
+  // half in the 32x32 accumulator
+  const bool owner = lane < 32;
   const int orow = lane & 31;
   const int oe = (orow & 3) + 4 * (orow >> 3), oh = (orow >> 2) & 1;
-  const int R_own = wid * 32 * QH + ohalf * 32 + orow;
+  const int R_own = wid * 32 + orow;
   float lst_d[KT];
   int lst_i[KT];
 #pragma unroll
@@ -709,30 +812,24 @@ __global__ void __launch_bounds__(64 * V2_WAVES / QH, 1) knn_scan_v2_kernel(KnnS
   // so that the compiler's vmcnt tracking does not wait on (our hand-counted
   // DMAs behind) their loads inside the tile loop
 #pragma unroll
-  for (int qh = 0; qh < QH; ++qh)
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb)
-      asm volatile("" : "+v"(af[qh][kb].x), "+v"(af[qh][kb].y), "+v"(af[qh][kb].z), "+v"(af[qh][kb].w));
+  for (int kb = 0; kb < KB; ++kb) asm volatile("" : "+v"(af[kb].x), "+v"(af[kb].y), "+v"(af[kb].z), "+v"(af[kb].w));
   __syncthreads();
   // prefilter: t = |g|^2 - 2 q.g <= crit - |q|^2 + slack, a superset of
   // d2 = (|q|^2 + |g|^2) - 2 q.g <= crit whatever the rounding of either form
   // (every magnitude is <= 2 (|q|^2 + gsq_max), each rounding <= 2^-24 of it)
   const float gmax = a.gsq_max_p ? *a.gsq_max_p : a.gsq_max;
-  float critp[QH][16];
+  float critp[16];
   auto load_crit = [&]() {
 #pragma unroll
-    for (int qh = 0; qh < QH; ++qh)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int R = wid * 32 * QH + qh * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        const float qs = s_qsq[R];
-        critp[qh][e] = (s_crit[R] - qs) + 0x1p-18f * (qs + gmax);
-      }
+    for (int e = 0; e < 16; ++e) {
+      const int R = wid * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+      const float qs = s_qsq[R];
+      critp[e] = (s_crit[R] - qs) + 0x1p-18f * (qs + gmax);
+    }
   };
   load_crit();
-  float* stg0 = s_stage + wid * QH * C::WSTG;  // half qh's staging at stg0 + qh * WSTG
-  float* sg = stg0 + (C::SROWS == 32 ? 32 : C::SROWS * C::SP);  // column c's |g|^2 at sg[c * gstr]
-  constexpr int gstr = C::SROWS == 32 ? C::SP : 1;
+  float* stg = s_stage + wid * C::WSTG;  // the wave's staging: row r's dot products at stg[r * SP + column]
+  float* sg = stg + 32;                  // column c's |g|^2 at sg[c * SP] (the padding of row c)
   const int q_own = qb + R_own;
   const float eps_own = q_own < a.Nq ? a.rel * sqrtf(a.qsq[q_own] * gmax) * 1.001f + 1e-3f : 0.f;
   float thr_g = s_thr[R_own];  // best shared bound seen (with thr0)
@@ -748,48 +845,18 @@ __global__ void __launch_bounds__(64 * V2_WAVES / QH, 1) knn_scan_v2_kernel(KnnS
     // B fragments PF reads ahead of their MFMA, pinned in that order (left
     // alone, the scheduler either hoists all KB reads and runs out of registers
     // or issues each read just one MFMA before its use and exposes the LDS latency)
-    // (KNN_PF: at 6 the kernel needs 256 VGPRs plus a 16-B spill whose reload
-    // before the first MFMA of every tile carried s_waitcnt vmcnt(0), draining
-    // the DMA ring each tile; 4 spills nothing)
-#ifndef KNN_PF
-#define KNN_PF 4
-#endif
     constexpr int PF = KB < KNN_PF ? KB : KNN_PF;
-    f32x16 acc[QH];
-#pragma unroll
-    for (int qh = 0; qh < QH; ++qh) acc[qh] = f32x16{};
+    f32x16 acc = f32x16{};
     uint4 bq[KB];
-#ifndef KNN_ABL
-#define KNN_ABL 0  // timing ablations of a diagnostic build only (1: no list work, 2: no MFMAs; tools/gpu/r4_knn_abl.sh)
-#endif
 #pragma unroll
     for (int j = 0; j < PF; ++j) bq[j] = *reinterpret_cast<const uint4*>(bp + j * 32);
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) {
       if (kb + PF < KB) bq[kb + PF] = *reinterpret_cast<const uint4*>(bp + (kb + PF) * 32);
-#pragma unroll
-      for (int qh = 0; qh < QH; ++qh) {
-        if (KNN_ABL & 2)
-          acc[qh][kb & 15] += __uint_as_float(bq[kb].x & 0x80000000u);
-        else if (QH == 2) {
-          // the A fragments stay in AGPRs (the MFMA reads them there; the builtin
-          // had the compiler copy each one to VGPRs first: 244 v_accvgpr_read
-          // per tile); acc in VGPRs for the prefilter
-          typedef unsigned kv_u4 __attribute__((ext_vector_type(4)));
-          const kv_u4 av = __builtin_bit_cast(kv_u4, af[qh][kb]), bv = __builtin_bit_cast(kv_u4, bq[kb]);
-          if (kb == 0)
-            asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=v"(acc[qh]) : "a"(av), "v"(bv));
-          else
-            asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc[qh]) : "a"(av), "v"(bv));
-        } else
-          acc[qh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&af[qh][kb]),
-                                                            *reinterpret_cast<const bf16x8*>(&bq[kb]), acc[qh], 0, 0, 0);
-      }
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&af[kb]),
+                                                    *reinterpret_cast<const bf16x8*>(&bq[kb]), acc, 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
-    // the hand-issued MFMAs' results are read by vector instructions next: the
-    // 16-pass XDL write -> VALU read hazard (18 wait states) the compiler cannot see
-    if (QH == 2 && !(KNN_ABL & 2)) asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" ::: "memory");
     const int bn = g0 + t * V2_ROWS;
     const bool cvalid = bn + r32 < a.Ng;
     const float gsq = cvalid ? *reinterpret_cast<const float*>(st + r32 * C::RB + 32 * KB) : INFINITY;
@@ -800,75 +867,46 @@ __global__ void __launch_bounds__(64 * V2_WAVES / QH, 1) knn_scan_v2_kernel(KnnS
     // tile t+3): the epilogue reads no stage, only gsq (saved above) and its own
     // wave's LDS.  An atomic of the previous epilogue forces the full wait.
     if (t + 1 < ntiles) {
-      if (t + 2 < ntiles && !__builtin_amdgcn_ballot_w64(atom)) {
-        if (C::NST == 4 && t + 3 < ntiles)
-          rvm_wait_n(ni_of(t + 2) + ni_of(t + 3));
-        else
-          rvm_wait_n(ni_of(t + 2));
-      } else {
+      if (t + 2 < ntiles && !__builtin_amdgcn_ballot_w64(atom))
+        rvm_wait_n(ni_of(t + 2));
+      else
         rvm_wait<0>();
-      }
     }
     atom = false;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of stage t (gsq) are done
     __syncthreads();
     bool any = false;
 #pragma unroll
-    for (int qh = 0; qh < QH; ++qh)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) any |= fmaf(-2.f, acc[qh][e], gsq) <= critp[qh][e];
-    if (KNN_ABL & 1) {
-      st_entries += __builtin_amdgcn_ballot_w64(any) ? 1u : 0u;
-      any = false;
-    }
+    for (int e = 0; e < 16; ++e) any |= fmaf(-2.f, acc[e], gsq) <= critp[e];
     if (__builtin_amdgcn_ballot_w64(any)) {
       ++st_entries;
       // stage the raw dot products of every row with a prefilter hit; the owner
       // of each row re-evaluates its hits exactly (d2 with the same formula as
       // knn_scan_kernel): list insertion, certainly-closer count, uncertain queue
       unsigned mymask = 0;
-      if (lane < 32) sg[r32 * gstr] = gsq;  // column r32's |g|^2 (INF past Ng)
+      if (lane < 32) sg[r32 * C::SP] = gsq;  // column r32's |g|^2 (INF past Ng)
 #pragma unroll
-      for (int qh = 0; qh < QH; ++qh) {
-        float* stg = stg0 + qh * C::WSTG;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const unsigned long long m = __builtin_amdgcn_ballot_w64(fmaf(-2.f, acc[qh][e], gsq) <= critp[qh][e]);
-          if (m) {
-            if (C::SROWS == 32) stg[((e & 3) + 8 * (e >> 2) + 4 * h) * C::SP + r32] = acc[qh][e];
-            if (oe == e && ohalf == qh) mymask = oh ? (unsigned)(m >> 32) : (unsigned)m;
-          }
+      for (int e = 0; e < 16; ++e) {
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(fmaf(-2.f, acc[e], gsq) <= critp[e]);
+        if (m) {
+          stg[((e & 3) + 8 * (e >> 2) + 4 * h) * C::SP + r32] = acc[e];
+          if (oe == e) mymask = oh ? (unsigned)(m >> 32) : (unsigned)m;
         }
       }
-      float* stg = stg0 + ohalf * C::WSTG;  // the owner's half
       bool changed = false;
       // every lane reads its (owner) row's state: lanes >= 32 mirror row lane - 32
       const float qs = s_qsq[R_own], hi = s_hi[R_own];
       float thr = s_thr[R_own];
-      // SROWS 16: two passes, the rows of lane half hp (h == hp) staged at
-      // (e & 3) + 4 (e >> 2), their owners (oh == hp) evaluating in between
-#pragma unroll
-      for (int hp = 0; hp < (C::SROWS == 32 ? 1 : 2); ++hp) {
-      if (C::SROWS == 16) {
-        if (hp) {  // pass 0's owners are done with the staging
-          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-        }
-        if (h == hp) {
-#pragma unroll
-          for (int e = 0; e < 16; ++e) stg[((e & 3) + 4 * (e >> 2)) * C::SP + r32] = acc[0][e];
-        }
-      }
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      if (owner && mymask && (C::SROWS == 32 || oh == hp)) {
+      if (owner && mymask) {
         const float lo = s_lo[R_own];
-        const float* srow = stg + (C::SROWS == 32 ? orow : oe) * C::SP;
+        const float* srow = stg + orow * C::SP;
         while (mymask) {
           const int c = __builtin_ctz(mymask);
           mymask &= mymask - 1;
           const bool valid = bn + c < a.Ng;
-          const float g2 = sg[c * gstr];
+          const float g2 = sg[c * C::SP];
           const float d2 = fmaf(-2.f, srow[c], qs + g2);
           if (CM) {
             if (d2 < thr && valid && q_own < a.Nq) {
@@ -912,21 +950,18 @@ __global__ void __launch_bounds__(64 * V2_WAVES / QH, 1) knn_scan_v2_kernel(KnnS
           s_crit[R_own] = fmaxf(thr, hi);
         }
       }
-      }
       if (__builtin_amdgcn_ballot_w64(changed)) {
         // refresh the prefilter bounds from the owner lanes' registers (readlane:
         // no fence, no LDS round trip); the same value load_crit() would read
         // (padding rows q >= Nq keep -INF, as load_crit() reads them)
         const float mine = q_own < a.Nq ? (fmaxf(thr, hi) - qs) + 0x1p-18f * (qs + gmax) : -INFINITY;
 #pragma unroll
-        for (int qh = 0; qh < QH; ++qh)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int r0 = qh * 32 + (e & 3) + 8 * (e >> 2);
-            const float n0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), r0));
-            const float n1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), r0 + 4));
-            critp[qh][e] = h ? n1 : n0;
-          }
+        for (int e = 0; e < 16; ++e) {
+          const int r0 = (e & 3) + 8 * (e >> 2);
+          const float n0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), r0));
+          const float n1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), r0 + 4));
+          critp[e] = h ? n1 : n0;
+        }
       }
     }
     if (a.kb && (((t & (KB_SYNC - 1)) == KB_SYNC - 1) || t + 1 == ntiles)) {
@@ -1020,86 +1055,25 @@ __global__ void __launch_bounds__(64 * V2_WAVES / QH, 1) knn_scan_v2_kernel(KnnS
   }
 }
 
-// queries per wave of the v2 scan: ARTSBIR_KNN_QH=2 (64, one wave per SIMD) or 1 (32)
-static int knn_qh() {
-  static const int qh = [] { const char* e = getenv("ARTSBIR_KNN_QH"); return e && atoi(e) == 2 ? 2 : 1; }();
-  return qh;
-}
-
-static void knn_scan_v2_launch(int Dp, unsigned grid, const KnnScanArgs& a, int stat, hipStream_t st) {
-  const dim3 g(grid);
-  if (knn_qh() == 2 && Dp == 512) {  // the register budget of two halves is sized for D = 512
-    hipLaunchKernelGGL((knn_scan_v2_kernel<32, 2>), g, dim3(256), 0, st, a, stat);
-    return;
-  }
+// one workgroup per (256-query tile, gallery chunk); Dp in {64, 128, 256, 512}
+// (artsbir_knn_scan_aug_supported)
+template <int CM>
+static void launch_scan_v2(int Dp, const KnnScanArgs& a, int stat, hipStream_t st) {
+  const dim3 g((unsigned)(a.nchunks * ((a.Nq + 255) / 256))), b(64 * V2_WAVES);
   switch (Dp) {
-    case 64: hipLaunchKernelGGL((knn_scan_v2_kernel<4, 1>), g, dim3(512), 0, st, a, stat); break;
-    case 128: hipLaunchKernelGGL((knn_scan_v2_kernel<8, 1>), g, dim3(512), 0, st, a, stat); break;
-    case 256: hipLaunchKernelGGL((knn_scan_v2_kernel<16, 1>), g, dim3(512), 0, st, a, stat); break;
-    default: hipLaunchKernelGGL((knn_scan_v2_kernel<32, 1>), g, dim3(512), 0, st, a, stat); break;
+    case 64: hipLaunchKernelGGL((knn_scan_v2_kernel<4, CM>), g, b, 0, st, a, stat); break;
+    case 128: hipLaunchKernelGGL((knn_scan_v2_kernel<8, CM>), g, b, 0, st, a, stat); break;
+    case 256: hipLaunchKernelGGL((knn_scan_v2_kernel<16, CM>), g, b, 0, st, a, stat); break;
+    default: hipLaunchKernelGGL((knn_scan_v2_kernel<32, CM>), g, b, 0, st, a, stat); break;
   }
 }
 
-static void knn_scan_v2_collect_launch(int Dp, unsigned grid, const KnnScanArgs& a, hipStream_t st) {
-  const dim3 g(grid);
-  switch (Dp) {
-    case 64: hipLaunchKernelGGL((knn_scan_v2_kernel<4, 1, 1>), g, dim3(512), 0, st, a, 0); break;
-    case 128: hipLaunchKernelGGL((knn_scan_v2_kernel<8, 1, 1>), g, dim3(512), 0, st, a, 0); break;
-    case 256: hipLaunchKernelGGL((knn_scan_v2_kernel<16, 1, 1>), g, dim3(512), 0, st, a, 0); break;
-    default: hipLaunchKernelGGL((knn_scan_v2_kernel<32, 1, 1>), g, dim3(512), 0, st, a, 0); break;
-  }
-}
-
-// augmented bf16 rows for knn_scan_v2: [n][Dp + 8], columns Dp..Dp+1 = f32 |x|^2
-// (normalize: unit rows for the cosine metric, as rows_prep_kernel)
-__global__ void rows_prep_aug_kernel(const float* __restrict__ x, int n, int D, int Dp, float* __restrict__ sq,
-                                     bf16* __restrict__ xa, int normalize) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-  if (row >= n) return;
-  const float* r = x + (long long)row * D;
-  const float sc = row_scale(r, D, lane, normalize);
-  bf16* o = xa + (long long)row * (Dp + 8);
-  float s = 0.f;
-  if (row_vec_ok(r, D)) {
-    // 8 consecutive columns per lane: two 16-B loads, one 16-B store of the
-    // bf16 copy (the row pitch 2 (Dp + 8) B is a multiple of 16)
-    for (int d0 = lane * 8; d0 < Dp; d0 += 512) {
-      float v[8];
-      row_load8(r, D, d0, sc, v);
-      bf16 h[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        s = fmaf(v[j], v[j], s);  // explicit fma: the same rounding in both kernels
-        h[j] = (bf16)v[j];
-      }
-      *reinterpret_cast<uint4*>(o + d0) = *reinterpret_cast<const uint4*>(h);
-    }
-  } else {
-    for (int d = lane; d < Dp; d += 64) {
-      const float v = d < D ? r[d] * sc : 0.f;
-      s = fmaf(v, v, s);
-      o[d] = (bf16)v;
-    }
-  }
-  s = warp_sum(s);
-  if (lane < 8) {
-    const unsigned bits = __float_as_uint(s);
-    unsigned short v = 0;
-    if (lane == 0) v = (unsigned short)(bits & 0xffffu);
-    if (lane == 1) v = (unsigned short)(bits >> 16);
-    reinterpret_cast<unsigned short*>(o)[Dp + lane] = v;
-  }
-  if (lane == 0) sq[row] = s;
-}
-
-// ------------------------------------------------------------ exact merge
+// -------------------------------------------------- exact merge (k <= 64)
 // one workgroup per query: exact f64 distances of every candidate, top-k by
 // (distance, global index), verification of the chunk lists.
 __global__ void __launch_bounds__(256) knn_merge_kernel(const float* __restrict__ q, const float* __restrict__ g, int D,
                                                         int nchunks, const float* __restrict__ cand_d,
-                                                        const int* __restrict__ cand_i, const float* __restrict__ qsq,
-                                                        float gsq_max, float rel, long long g_base, int k,
+                                                        const int* __restrict__ cand_i, long long g_base, int k,
                                                         long long* __restrict__ out_i, double* __restrict__ out_d,
                                                         int* __restrict__ flag, int metric,
                                                         const float* __restrict__ qeps, long long n_g) {
@@ -1112,7 +1086,7 @@ __global__ void __launch_bounds__(256) knn_merge_kernel(const float* __restrict_
   const float* qr = q + (long long)qi * D;
   const float* cd = cand_d + (long long)qi * nc;
   const int* ci = cand_i + (long long)qi * nc;
-  const double eps = qeps ? (double)qeps[qi] : rel * sqrt((double)qsq[qi] * gsq_max) + 1e-3;
+  const double eps = qeps[qi];
   __shared__ double rd[4];
   __shared__ int ri[4], rslot[4];
   // (1) a_k = k-th smallest approximate value: the k items with approx <= a_k have
@@ -1293,7 +1267,6 @@ template <int NPL>
 __global__ void __launch_bounds__(64) knn_merge_wave_kernel(const float* __restrict__ q, const float* __restrict__ g,
                                                             int D, int nchunks, const float* __restrict__ cand_d,
                                                             const int* __restrict__ cand_i,
-                                                            const float* __restrict__ qsq, float gsq_max, float rel,
                                                             long long g_base, int k, long long* __restrict__ out_i,
                                                             double* __restrict__ out_d, int* __restrict__ flag,
                                                             int metric, const float* __restrict__ qeps, long long n_g,
@@ -1306,7 +1279,7 @@ __global__ void __launch_bounds__(64) knn_merge_wave_kernel(const float* __restr
   const float* qr = q + (long long)qi * D;
   const float* cd = cand_d + (long long)qi * nc;
   const int* ci = cand_i + (long long)qi * nc;
-  const double eps = qeps ? (double)qeps[qi] : rel * sqrt((double)qsq[qi] * gsq_max) + 1e-3;
+  const double eps = qeps[qi];
   float av[NPL];
   int ai[NPL];
   unsigned nvalid = 0;
@@ -1418,16 +1391,15 @@ __global__ void __launch_bounds__(64) knn_merge_wave_kernel(const float* __restr
 
 // launches the one-wave merge when the candidates fit its registers (nc <= 1024)
 static bool launch_merge_wave(int Q, hipStream_t st, const float* q, const float* g, int D, int nchunks,
-                              const float* cand_d, const int* cand_i, const float* qsq, float gsq_max, float rel,
-                              long long g_base, int k, long long* out_i, double* out_d, int* flag, int metric,
-                              const float* qeps, long long n_g) {
+                              const float* cand_d, const int* cand_i, long long g_base, int k, long long* out_i,
+                              double* out_d, int* flag, int metric, const float* qeps, long long n_g) {
   static const bool on = [] { const char* e = getenv("ARTSBIR_KNN_MERGE_WAVE"); return !e || atoi(e) != 0; }();
   const int nc = nchunks * KT;
   if (!on || nc > 1024) return false;
   const size_t sh = (size_t)nc * (sizeof(double) + sizeof(int));
-#define ARTSBIR_MW(NPL)                                                                                            \
-  hipLaunchKernelGGL(knn_merge_wave_kernel<NPL>, dim3(Q), dim3(64), sh, st, q, g, D, nchunks, cand_d, cand_i, qsq, \
-                     gsq_max, rel, g_base, k, out_i, out_d, flag, metric, qeps, n_g, knn_stat_on() ? 1 : 0)
+#define ARTSBIR_MW(NPL)                                                                                               \
+  hipLaunchKernelGGL(knn_merge_wave_kernel<NPL>, dim3(Q), dim3(64), sh, st, q, g, D, nchunks, cand_d, cand_i, g_base, \
+                     k, out_i, out_d, flag, metric, qeps, n_g, knn_stat_on() ? 1 : 0)
   if (nc <= 128) ARTSBIR_MW(2);
   else if (nc <= 256) ARTSBIR_MW(4);
   else if (nc <= 512) ARTSBIR_MW(8);
@@ -1436,6 +1408,8 @@ static bool launch_merge_wave(int Q, hipStream_t st, const float* q, const float
   return true;
 }
 
+// ------------------------------------------------------------- rank count
+// cnt[q] starts as the scans' count of items certainly closer than the positive
 // exact checks of the uncertain items of the rank count
 __global__ void knn_uncertain_kernel(const float* __restrict__ q, const float* __restrict__ g, int D,
                                      const int* __restrict__ unc, int unc_cap, const double* __restrict__ dpos,
@@ -1450,82 +1424,6 @@ __global__ void knn_uncertain_kernel(const float* __restrict__ q, const float* _
     const long long ggi = g_base + gi;
     if (lane == 0 && (d < dp || (d == dp && ggi < pos[qi]))) atomicAdd(cnt + qi, 1);
   }
-}
-
-// exhaustive exact scan of one query (fallback for flagged queries, and the
-// small-gallery path): writes all exact distances
-__global__ void knn_exact_all_kernel(const float* __restrict__ q, const float* __restrict__ g, int D, int n,
-                                     double* __restrict__ out, int metric) {
-  const int lane = threadIdx.x & 63;
-  for (int i = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); i < n; i += gridDim.x * (blockDim.x / 64)) {
-    const double d = exact_key(q, g + (long long)i * D, D, lane, metric);
-    if (lane == 0) out[i] = d;
-  }
-}
-
-// nn.PairwiseDistance(p=2, eps=1e-6) with broadcasting of a one-row operand,
-// f32 arithmetic as torch does it (utils.euclidean_distance)
-__global__ void pairwise_l2_kernel(const float* __restrict__ x1, long long n1, const float* __restrict__ x2, long long n2,
-                                   int D, float eps, float* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const long long n = n1 > n2 ? n1 : n2;
-  for (long long i = blockIdx.x * (long long)(blockDim.x / 64) + (threadIdx.x >> 6); i < n;
-       i += (long long)gridDim.x * (blockDim.x / 64)) {
-    const float* a = x1 + (n1 == 1 ? 0 : i) * D;
-    const float* b = x2 + (n2 == 1 ? 0 : i) * D;
-    float s = 0.f;
-    for (int d = lane; d < D; d += 64) {
-      const float t = a[d] - b[d] + eps;
-      s += t * t;
-    }
-    s = warp_sum(s);
-    if (lane == 0) out[i] = sqrtf(s);
-  }
-}
-
-// ------------------------------------------- one-call top-k (no host syncs)
-// The kernels below complete artsbir_pairwise_l2_topk: every decision the
-// multi-call protocol made on the host (max |g|^2, the uncertain-queue overflow,
-// flagged queries) is made on the device.
-
-// min and max of |g|^2 over the gallery into ext[0] (max), ext[1] (min) as f32
-// bit patterns (non-negative floats order like their bits); ext preset to (0, +INF)
-__global__ void sq_minmax_kernel(const float* __restrict__ sq, long long n, unsigned* __restrict__ ext) {
-  float mx = 0.f, mn = INFINITY;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    mx = fmaxf(mx, sq[i]);
-    mn = fminf(mn, sq[i]);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    mn = fminf(mn, __shfl_xor(mn, o, 64));
-  }
-  // one atomic pair per workgroup (the atomics on two words serialise: one pair
-  // per wave of a 1024-workgroup grid took ~95 us)
-  __shared__ float smx[16], smn[16];
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { smx[w] = mx; smn[w] = mn; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) { mx = fmaxf(mx, smx[i]); mn = fminf(mn, smn[i]); }
-    atomicMax(ext, __float_as_uint(mx));
-    atomicMin(ext + 1, __float_as_uint(mn));
-  }
-}
-
-// per-query eps (query_eps) and the initial dpos (caller's value for shard
-// calls, else -1); cnt and the uncertain-queue length start at 0
-__global__ void knn_init_kernel(const float* __restrict__ qsq, const unsigned* __restrict__ ext, int nq, float rel,
-                                int metric, const double* __restrict__ dpos_in, float* __restrict__ qeps,
-                                double* __restrict__ dpos, int* __restrict__ cnt, int* __restrict__ unc_n) {
-  const int qi = blockIdx.x * blockDim.x + threadIdx.x;
-  if (qi == 0) *unc_n = 0;
-  if (qi >= nq) return;
-  const float gmax = __uint_as_float(ext[0]), gmin = __uint_as_float(ext[1]);
-  qeps[qi] = (float)(query_eps(qsq[qi], gmax, gmin, rel, metric) * (1.0 + 1e-6));
-  dpos[qi] = dpos_in ? dpos_in[qi] : -1.0;
-  cnt[qi] = 0;
 }
 
 // uncertain-queue overflow (more uncertain items than unc_cap): recount every
@@ -1562,109 +1460,13 @@ __global__ void __launch_bounds__(256) knn_count_exhaustive_kernel(const float* 
   }
 }
 
-// exhaustive exact top-k of the flagged queries (a chunk list could have hidden
-// a true top-k item, or the gallery is too small for the lists): every wave
-// keeps a sorted (key, index) list of the k best rows it sees, lane i holding
-// entry i (k <= 64), inserted by ballot + shuffle; lists to part[q][W][k]
-constexpr int KNN_XB = 8;  // workgroups (x 4 waves) per flagged query
-
-__global__ void __launch_bounds__(256) knn_exact_topk_part_kernel(const float* __restrict__ q,
-                                                                  const float* __restrict__ g, int D, long long n,
-                                                                  int k, int metric, const int* __restrict__ flag,
-                                                                  double* __restrict__ pkey,
-                                                                  long long* __restrict__ pidx) {
-  const int qi = blockIdx.y;
-  if (!flag[qi]) return;
-  const int lane = threadIdx.x & 63;
-  const int W = gridDim.x * 4;
-  const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
-  double lk = INFINITY;
-  long long li = 0x7fffffffffffffffLL;
-  for (long long r = w; r < n; r += W) {
-    const double key = exact_key(q + (long long)qi * D, g + r * D, D, lane, metric);
-    const double kk = __shfl(lk, k - 1, 64);
-    const long long ki = __shfl(li, k - 1, 64);
-    if (key < kk || (key == kk && r < ki)) {  // wave-uniform
-      const bool before = lane < k && (lk < key || (lk == key && li < r));
-      const int at = __popcll(__builtin_amdgcn_ballot_w64(before));
-      const double uk = __shfl_up(lk, 1, 64);
-      const long long ui = __shfl_up(li, 1, 64);
-      if (lane == at) {
-        lk = key;
-        li = r;
-      } else if (lane > at && lane < k) {
-        lk = uk;
-        li = ui;
-      }
-    }
-  }
-  if (lane < k) {
-    const long long o = ((long long)qi * W + w) * k + lane;
-    pkey[o] = lk;
-    pidx[o] = li == 0x7fffffffffffffffLL ? -1 : li;
-  }
-}
-
-// k smallest (key, index) of nl lists of k entries (index -1 = empty) -> out;
-// one workgroup per row of lists; rows with flag == 0 are left alone (flag ==
-// nullptr: every row).  Shared by the flagged-query fallback and
-// artsbir_topk_merge (per-shard top-k lists of a sharded gallery).
-// Entry j of list l of row qi is at qi * s_row + l * s_list + j.
-__global__ void __launch_bounds__(256) topk_lists_merge_kernel(const double* __restrict__ key,
-                                                               const long long* __restrict__ idx, int nl, int k,
-                                                               long long s_row, long long s_list,
-                                                               const int* __restrict__ flag, long long idx_base,
-                                                               long long* __restrict__ out_i,
-                                                               double* __restrict__ out_d) {
-  const int qi = blockIdx.x;
-  if (flag && !flag[qi]) return;
-  extern __shared__ char sm[];
-  unsigned char* used = reinterpret_cast<unsigned char*>(sm);
-  const int nc = nl * k;
-  const double* kr = key + (long long)qi * s_row;
-  const long long* ir = idx + (long long)qi * s_row;
-  auto at = [&](int c) { return (long long)(c / k) * s_list + (c % k); };
-  for (int c = threadIdx.x; c < nc; c += blockDim.x) used[c] = ir[at(c)] < 0 ? 1 : 0;
-  __syncthreads();
-  __shared__ double rd[4];
-  __shared__ long long ri[4];
-  __shared__ int rs[4];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  for (int r = 0; r < k; ++r) {
-    double bd = INFINITY;
-    long long bi = 0x7fffffffffffffffLL;
-    int bs = -1;
-    for (int c = threadIdx.x; c < nc; c += blockDim.x) {
-      if (used[c]) continue;
-      const double d = kr[at(c)];
-      const long long i = ir[at(c)];
-      if (bs < 0 || d < bd || (d == bd && i < bi)) { bd = d; bi = i; bs = c; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const double od = __shfl_xor(bd, o, 64);
-      const long long oi = __shfl_xor(bi, o, 64);
-      const int os = __shfl_xor(bs, o, 64);
-      if (os >= 0 && (bs < 0 || od < bd || (od == bd && oi < bi))) { bd = od; bi = oi; bs = os; }
-    }
-    if (lane == 0) { rd[wid] = bd; ri[wid] = bi; rs[wid] = bs; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double b = rd[0];
-      long long bi2 = ri[0];
-      int bs2 = rs[0];
-      for (int w = 1; w < (int)blockDim.x / 64; ++w)
-        if (rs[w] >= 0 && (bs2 < 0 || rd[w] < b || (rd[w] == b && ri[w] < bi2))) { b = rd[w]; bi2 = ri[w]; bs2 = rs[w]; }
-      out_i[(long long)qi * k + r] = bs2 >= 0 ? idx_base + bi2 : -1;
-      out_d[(long long)qi * k + r] = bs2 >= 0 ? b : INFINITY;
-      if (bs2 >= 0) used[bs2] = 1;
-    }
-    __syncthreads();
-  }
+__global__ void rank_out_kernel(const int* __restrict__ cnt, int nq, long long* __restrict__ out) {
+  const int qi = blockIdx.x * blockDim.x + threadIdx.x;
+  if (qi < nq) out[qi] = cnt[qi];
 }
 
 // ------------------------------------------------- large k (65 .. 1024)
-// The wave-resident merge and fallback above stop at k = 64.  For larger k the
+// The wave-resident merge above and its fallback stop at k = 64.  For larger k the
 // one-call path keeps the scan and its chunk lists only to find a per-query cut:
 //   knn_lk_thresh_kernel   T = k-th smallest approximate d2 of the union of the
 //                          chunk lists (>= the gallery's k-th smallest a_k), cut =
@@ -1676,7 +1478,8 @@ __global__ void __launch_bounds__(256) topk_lists_merge_kernel(const double* __r
 //                          index) in LDS, the first k written; a query whose
 //                          buffer overflowed or holds fewer than min(k, N) rows
 //                          is flagged instead;
-//   knn_lk_exhaustive_kernel  the flagged queries, by an exact scan of the gallery.
+//   knn_lk_exhaustive_kernel  (under the fallbacks) the flagged queries, by an
+//                          exact scan of the gallery.
 // A gallery of at most cand_cap rows skips the cut: every row is a candidate.
 constexpr int LK_SORT = 4096;  // entries knn_lk_select_kernel sorts (48 KB of LDS): the largest cand_cap
 constexpr int LK_PAD = 0x7fffffff;
@@ -1812,6 +1615,111 @@ __global__ void __launch_bounds__(512) knn_lk_select_kernel(const float* __restr
   }
 }
 
+// -------------------------------------- fallbacks: the flagged queries
+// k <= 64: knn_exact_topk_part_kernel + topk_lists_merge_kernel; larger k:
+// knn_lk_exhaustive_kernel.  All three return at once for an unflagged query.
+//
+// exhaustive exact top-k of the flagged queries (a chunk list could have hidden
+// a true top-k item, or the gallery is too small for the lists): every wave
+// keeps a sorted (key, index) list of the k best rows it sees, lane i holding
+// entry i (k <= 64), inserted by ballot + shuffle; lists to part[q][W][k]
+constexpr int KNN_XB = 8;  // workgroups (x 4 waves) per flagged query
+
+__global__ void __launch_bounds__(256) knn_exact_topk_part_kernel(const float* __restrict__ q,
+                                                                  const float* __restrict__ g, int D, long long n,
+                                                                  int k, int metric, const int* __restrict__ flag,
+                                                                  double* __restrict__ pkey,
+                                                                  long long* __restrict__ pidx) {
+  const int qi = blockIdx.y;
+  if (!flag[qi]) return;
+  const int lane = threadIdx.x & 63;
+  const int W = gridDim.x * 4;
+  const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+  double lk = INFINITY;
+  long long li = 0x7fffffffffffffffLL;
+  for (long long r = w; r < n; r += W) {
+    const double key = exact_key(q + (long long)qi * D, g + r * D, D, lane, metric);
+    const double kk = __shfl(lk, k - 1, 64);
+    const long long ki = __shfl(li, k - 1, 64);
+    if (key < kk || (key == kk && r < ki)) {  // wave-uniform
+      const bool before = lane < k && (lk < key || (lk == key && li < r));
+      const int at = __popcll(__builtin_amdgcn_ballot_w64(before));
+      const double uk = __shfl_up(lk, 1, 64);
+      const long long ui = __shfl_up(li, 1, 64);
+      if (lane == at) {
+        lk = key;
+        li = r;
+      } else if (lane > at && lane < k) {
+        lk = uk;
+        li = ui;
+      }
+    }
+  }
+  if (lane < k) {
+    const long long o = ((long long)qi * W + w) * k + lane;
+    pkey[o] = lk;
+    pidx[o] = li == 0x7fffffffffffffffLL ? -1 : li;
+  }
+}
+
+// k smallest (key, index) of nl lists of k entries (index -1 = empty) -> out;
+// one workgroup per row of lists; rows with flag == 0 are left alone (flag ==
+// nullptr: every row).  Shared by the flagged-query fallback and
+// artsbir_topk_merge (per-shard top-k lists of a sharded gallery).
+// Entry j of list l of row qi is at qi * s_row + l * s_list + j.
+__global__ void __launch_bounds__(256) topk_lists_merge_kernel(const double* __restrict__ key,
+                                                               const long long* __restrict__ idx, int nl, int k,
+                                                               long long s_row, long long s_list,
+                                                               const int* __restrict__ flag, long long idx_base,
+                                                               long long* __restrict__ out_i,
+                                                               double* __restrict__ out_d) {
+  const int qi = blockIdx.x;
+  if (flag && !flag[qi]) return;
+  extern __shared__ char sm[];
+  unsigned char* used = reinterpret_cast<unsigned char*>(sm);
+  const int nc = nl * k;
+  const double* kr = key + (long long)qi * s_row;
+  const long long* ir = idx + (long long)qi * s_row;
+  auto at = [&](int c) { return (long long)(c / k) * s_list + (c % k); };
+  for (int c = threadIdx.x; c < nc; c += blockDim.x) used[c] = ir[at(c)] < 0 ? 1 : 0;
+  __syncthreads();
+  __shared__ double rd[4];
+  __shared__ long long ri[4];
+  __shared__ int rs[4];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (int r = 0; r < k; ++r) {
+    double bd = INFINITY;
+    long long bi = 0x7fffffffffffffffLL;
+    int bs = -1;
+    for (int c = threadIdx.x; c < nc; c += blockDim.x) {
+      if (used[c]) continue;
+      const double d = kr[at(c)];
+      const long long i = ir[at(c)];
+      if (bs < 0 || d < bd || (d == bd && i < bi)) { bd = d; bi = i; bs = c; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double od = __shfl_xor(bd, o, 64);
+      const long long oi = __shfl_xor(bi, o, 64);
+      const int os = __shfl_xor(bs, o, 64);
+      if (os >= 0 && (bs < 0 || od < bd || (od == bd && oi < bi))) { bd = od; bi = oi; bs = os; }
+    }
+    if (lane == 0) { rd[wid] = bd; ri[wid] = bi; rs[wid] = bs; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double b = rd[0];
+      long long bi2 = ri[0];
+      int bs2 = rs[0];
+      for (int w = 1; w < (int)blockDim.x / 64; ++w)
+        if (rs[w] >= 0 && (bs2 < 0 || rd[w] < b || (rd[w] == b && ri[w] < bi2))) { b = rd[w]; bi2 = ri[w]; bs2 = rs[w]; }
+      out_i[(long long)qi * k + r] = bs2 >= 0 ? idx_base + bi2 : -1;
+      out_d[(long long)qi * k + r] = bs2 >= 0 ? b : INFINITY;
+      if (bs2 >= 0) used[bs2] = 1;
+    }
+    __syncthreads();
+  }
+}
+
 // exhaustive exact top-k of a flagged query, k <= 1024 (correct, not fast): one
 // workgroup streams the gallery in batches of 1024 rows; LDS holds the 1024 best
 // (key, index) so far and the batch's keys, and one sort of the 2048 keeps the best
@@ -1848,6 +1756,27 @@ __global__ void __launch_bounds__(1024) knn_lk_exhaustive_kernel(const float* __
   }
 }
 
+// ----------------------------------- kernels of the small entry points
+// nn.PairwiseDistance(p=2, eps=1e-6) with broadcasting of a one-row operand,
+// f32 arithmetic as torch does it (utils.euclidean_distance)
+__global__ void pairwise_l2_kernel(const float* __restrict__ x1, long long n1, const float* __restrict__ x2, long long n2,
+                                   int D, float eps, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const long long n = n1 > n2 ? n1 : n2;
+  for (long long i = blockIdx.x * (long long)(blockDim.x / 64) + (threadIdx.x >> 6); i < n;
+       i += (long long)gridDim.x * (blockDim.x / 64)) {
+    const float* a = x1 + (n1 == 1 ? 0 : i) * D;
+    const float* b = x2 + (n2 == 1 ? 0 : i) * D;
+    float s = 0.f;
+    for (int d = lane; d < D; d += 64) {
+      const float t = a[d] - b[d] + eps;
+      s += t * t;
+    }
+    s = warp_sum(s);
+    if (lane == 0) out[i] = sqrtf(s);
+  }
+}
+
 // out[qi][i] = exact key of (query qi, row i), every pair (one wave per key)
 __global__ void knn_exact_keys_kernel(const float* __restrict__ q, int nq, const float* __restrict__ g, long long n,
                                       int D, int metric, double* __restrict__ out) {
@@ -1877,160 +1806,13 @@ __global__ void positive_key_kernel(const float* __restrict__ q, const float* __
   if (lane == 0) out[qi] = d;
 }
 
-__global__ void rank_out_kernel(const int* __restrict__ cnt, int nq, long long* __restrict__ out) {
-  const int qi = blockIdx.x * blockDim.x + threadIdx.x;
-  if (qi < nq) out[qi] = cnt[qi];
-}
-
 }  // namespace artsbir
 
 using namespace artsbir;
 
-extern "C" int artsbir_pairwise_l2(const float* x1, long long n1, const float* x2, long long n2, int D, float eps,
-                                   float* out, void* stream) {
-  if (!(n1 == n2 || n1 == 1 || n2 == 1)) { set_error("pairwise_l2: shapes %lld vs %lld", n1, n2); return -1; }
-  const long long n = n1 > n2 ? n1 : n2;
-  long long grid = (n + 3) / 4;
-  if (grid > 65536) grid = 65536;
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(pairwise_l2_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x1, n1, x2, n2, D, eps, out);
-  ARTSBIR_CHECK_LAUNCH("pairwise_l2");
-  return 0;
-}
-
-extern "C" int artsbir_rows_prep(int dtype, const float* x, int n, int D, float* sq, void* xc, int ldc, void* stream) {
-  const unsigned grid = (unsigned)((n + 3) / 4);
-  if (n <= 0) return 0;
-  if (ldc < D) ldc = D;
-  if (dtype == ARTSBIR_DT_BF16)
-    hipLaunchKernelGGL(rows_prep_kernel<bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, n, D, sq, (bf16*)xc, ldc, 0);
-  else
-    hipLaunchKernelGGL(rows_prep_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, n, D, sq, (float*)xc, ldc, 0);
-  ARTSBIR_CHECK_LAUNCH("rows_prep");
-  return 0;
-}
-
-extern "C" int artsbir_knn_band(const float* q, const float* g, const long long* pos, long long g_base, long long n_g,
-                                const float* qsq, float gsq_max, int nq, int D, float rel, double* dpos, float* lo,
-                                float* hi, void* stream) {
-  if (nq <= 0) return 0;
-  hipLaunchKernelGGL(knn_band_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, (hipStream_t)stream, q, g, pos, g_base,
-                     n_g, qsq, gsq_max, nq, D, rel, dpos, lo, hi, 0, nullptr);
-  ARTSBIR_CHECK_LAUNCH("knn_band");
-  return 0;
-}
-
-extern "C" int artsbir_knn_band_from_dpos(const double* dpos, const float* qsq, float gsq_max, int nq, float rel,
-                                          float* lo, float* hi, void* stream) {
-  if (nq <= 0) return 0;
-  hipLaunchKernelGGL(knn_band_from_dpos_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     dpos, qsq, gsq_max, nq, rel, lo, hi);
-  ARTSBIR_CHECK_LAUNCH("knn_band_from_dpos");
-  return 0;
-}
-
-extern "C" int artsbir_knn_candidates_per_query(int ng, int tiles_per_chunk) {
-  const int tiles = (ng + 127) / 128;
-  const int nchunks = (tiles + tiles_per_chunk - 1) / tiles_per_chunk;
-  return nchunks * KT;
-}
-
-extern "C" int artsbir_knn_scan(int dtype, const void* qc, const void* gc, const float* qsq, const float* gsq, int nq,
-                                int ng, int D, int tiles_per_chunk, const float* lo, const float* hi, int* cnt, int* unc,
-                                int unc_cap, float* cand_d, int* cand_i, void* stream) {
-  const int EPC = dtype == ARTSBIR_DT_BF16 ? 8 : 4;
-  if (D % (8 * EPC)) { set_error("knn_scan: D=%d must be a multiple of %d", D, 8 * EPC); return -1; }
-  if (nq <= 0 || ng <= 0) return 0;
-  KnnScanArgs a;
-  a.q = qc; a.g = gc; a.qsq = qsq; a.gsq = gsq; a.gsq_max = 0.f; a.gsq_max_p = nullptr; a.thr0 = nullptr; a.kb = nullptr; a.hist = nullptr; a.hbase = nullptr; a.kq = 0; a.rel = 0.f; a.Nq = nq; a.Ng = ng; a.D = D;
-  a.tiles_per_chunk = tiles_per_chunk;
-  const int tiles = (ng + 127) / 128;
-  a.nchunks = (tiles + tiles_per_chunk - 1) / tiles_per_chunk;
-  a.lo = lo; a.hi = hi; a.cnt = cnt; a.unc = unc; a.unc_cap = unc_cap; a.cand_d = cand_d; a.cand_i = cand_i; a.col_n = nullptr; a.col_i = nullptr; a.col_cap = 0;
-  const unsigned grid = (unsigned)(a.nchunks * ((nq + 127) / 128));
-  if (dtype == ARTSBIR_DT_BF16)
-    hipLaunchKernelGGL(knn_scan_kernel<bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(knn_scan_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-  ARTSBIR_CHECK_LAUNCH("knn_scan");
-  return 0;
-}
-
-extern "C" int artsbir_knn_merge(const float* q, const float* g, int D, int nq, int nchunks, const float* cand_d,
-                                 const int* cand_i, const float* qsq, float gsq_max, float rel, long long g_base, int k,
-                                 long long* out_i, double* out_d, int* flag, void* stream) {
-  if (nq <= 0) return 0;
-  if (k > nchunks * KT) { set_error("knn_merge: k=%d exceeds candidates %d", k, nchunks * KT); return -1; }
-  const size_t sh = (size_t)nchunks * KT * (sizeof(double) + sizeof(int));
-  if (sh > 60000) { set_error("knn_merge: too many candidates (%d chunks)", nchunks); return -1; }
-  if (!launch_merge_wave(nq, (hipStream_t)stream, q, g, D, nchunks, cand_d, cand_i, qsq, gsq_max, rel, g_base, k, out_i,
-                         out_d, flag, 0, nullptr, 0LL))
-    hipLaunchKernelGGL(knn_merge_kernel, dim3(nq), dim3(256), sh, (hipStream_t)stream, q, g, D, nchunks, cand_d, cand_i,
-                       qsq, gsq_max, rel, g_base, k, out_i, out_d, flag, 0, nullptr, 0LL);
-  ARTSBIR_CHECK_LAUNCH("knn_merge");
-  return 0;
-}
-
-extern "C" int artsbir_knn_uncertain(const float* q, const float* g, int D, const int* unc, int unc_cap,
-                                     const double* dpos, const long long* pos, long long g_base, int* cnt, void* stream) {
-  hipLaunchKernelGGL(knn_uncertain_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, q, g, D, unc, unc_cap, dpos,
-                     pos, g_base, cnt, 0);
-  ARTSBIR_CHECK_LAUNCH("knn_uncertain");
-  return 0;
-}
-
-extern "C" int artsbir_knn_exact_all(const float* q, const float* g, int D, int n, double* out, void* stream) {
-  if (n <= 0) return 0;
-  unsigned grid = (unsigned)((n + 3) / 4);
-  if (grid > 65536) grid = 65536;
-  hipLaunchKernelGGL(knn_exact_all_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, q, g, D, n, out, 0);
-  ARTSBIR_CHECK_LAUNCH("knn_exact_all");
-  return 0;
-}
-
-extern "C" int artsbir_rows_prep_aug(const float* x, int n, int D, int Dp, float* sq, void* xa, void* stream) {
-  if (Dp < D || Dp % 16) { set_error("rows_prep_aug: Dp=%d must be >= D=%d and a multiple of 16", Dp, D); return -1; }
-  if (n <= 0) return 0;
-  hipLaunchKernelGGL(rows_prep_aug_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, n, D, Dp,
-                     sq, (bf16*)xa, 0);
-  ARTSBIR_CHECK_LAUNCH("rows_prep_aug");
-  return 0;
-}
-
-extern "C" int artsbir_knn_scan_aug_supported(int Dp) { return Dp == 64 || Dp == 128 || Dp == 256 || Dp == 512; }
-
-extern "C" int artsbir_knn_scan_aug(const void* qc, const void* ga, const float* qsq, float gsq_max, int nq, int ng,
-                                    int Dp, int tiles_per_chunk, const float* thr0, unsigned* kbound, int k, float rel,
-                                    const float* lo, const float* hi, int* cnt, int* unc, int unc_cap, float* cand_d,
-                                    int* cand_i, void* stream) {
-  if (!artsbir_knn_scan_aug_supported(Dp)) { set_error("knn_scan_aug: Dp=%d not in {64,128,256,512}", Dp); return -1; }
-  if (tiles_per_chunk <= 0 || (long long)tiles_per_chunk * 128 * (2LL * Dp + 16) > 0x7fffffffLL) {
-    set_error("knn_scan_aug: tiles_per_chunk=%d out of range", tiles_per_chunk);
-    return -1;
-  }
-  if (kbound && (k < 1 || k > KT)) { set_error("knn_scan_aug: k=%d must be in 1..%d with a shared bound", k, KT); return -1; }
-  if (nq <= 0 || ng <= 0) return 0;
-  KnnScanArgs a;
-  a.q = qc; a.g = ga; a.qsq = qsq; a.gsq = nullptr; a.gsq_max = gsq_max; a.gsq_max_p = nullptr; a.thr0 = thr0; a.kb = kbound; a.hist = nullptr; a.hbase = nullptr; a.kq = k; a.rel = rel; a.Nq = nq; a.Ng = ng; a.D = Dp;
-  a.tiles_per_chunk = tiles_per_chunk;
-  const int tiles = (ng + 127) / 128;
-  a.nchunks = (tiles + tiles_per_chunk - 1) / tiles_per_chunk;
-  a.lo = lo; a.hi = hi; a.cnt = cnt; a.unc = unc; a.unc_cap = unc_cap; a.cand_d = cand_d; a.cand_i = cand_i; a.col_n = nullptr; a.col_i = nullptr; a.col_cap = 0;
-  const unsigned grid = (unsigned)(a.nchunks * ((nq + 255) / 256));
-  knn_scan_v2_launch(Dp, grid, a, 0, (hipStream_t)stream);
-  ARTSBIR_CHECK_LAUNCH("knn_scan_aug");
-  return 0;
-}
-
-// ---------------------------------------------------------------------------
-// One-call exact top-k + rank of the positive (the drop-in for the per-query
-// loop of inference.py:30-69: utils.euclidean_distance / cosine_distance of
-// [1,D] vs [N,D], topk(N) -> position of the positive, topk(k)).  Launch
-// sequence (all on `stream`, no host synchronisation):
-//   rows_prep(q), rows_prep_aug(g) [unit rows for cosine] -> min/max |g|^2 ->
-//   per-query eps + dpos init -> band (exact key of the positive) -> MFMA scan
-//   -> exact merge -> uncertain checks -> overflow recount -> exhaustive top-k
-//   of flagged queries -> ranks.
+// --------------------------------------------------------------- the plan
+// Chunking, path (v1 / v2 scan, k <= 64 / large k) and workspace layout of one
+// call; the workspace query and the call itself both come here.
 namespace {
 // optional HIP-event timing of the scan kernel inside artsbir_pairwise_l2_topk
 // (bench.py prices the scan against the MFMA roof with it)
@@ -2151,15 +1933,11 @@ int topk_plan(int dtype, int Q, long long N, int D, int k, int tpc_req, TopkPlan
 }
 }  // namespace
 
-extern "C" int artsbir_knn_stat_read(unsigned long long* out4, int reset) {
-  if (hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_knn_stat), sizeof(unsigned long long) * 4) != hipSuccess) return -1;
-  if (reset) {
-    static const unsigned long long z[4] = {0, 0, 0, 0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_knn_stat), z, sizeof(z)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-
+// --------------------------------------------------------------- the call
+// One-call exact top-k + rank of the positive (the drop-in for the per-query
+// loop of inference.py:30-69: utils.euclidean_distance / cosine_distance of
+// [1,D] vs [N,D], topk(N) -> position of the positive, topk(k)).  Everything on
+// `stream`, in the order of the stages at the top of the file.
 extern "C" long long artsbir_pairwise_l2_topk_workspace(int dtype, int Q, long long N, int D, int k,
                                                         int tiles_per_chunk) {
   TopkPlan p;
@@ -2216,16 +1994,11 @@ extern "C" int artsbir_pairwise_l2_topk(int dtype, int metric, const float* q, i
     return -2;
   }
   const unsigned gq = (unsigned)((Q + 3) / 4), gg = (unsigned)((N + 3) / 4);
-  if (dtype == ARTSBIR_DT_BF16)
-    hipLaunchKernelGGL(rows_prep_kernel<bf16>, dim3(gq), dim3(256), 0, st, q, Q, D, qsq, (bf16*)qc, p.Dp, metric);
-  else
-    hipLaunchKernelGGL(rows_prep_kernel<float>, dim3(gq), dim3(256), 0, st, q, Q, D, qsq, (float*)qc, p.Dp, metric);
+  launch_rows_prep(dtype, q, Q, D, qsq, qc, p.Dp, metric, st);
   if (p.v2)
     hipLaunchKernelGGL(rows_prep_aug_kernel, dim3(gg), dim3(256), 0, st, g, ng, D, p.Dp, gsq, (bf16*)gc, metric);
-  else if (dtype == ARTSBIR_DT_BF16)
-    hipLaunchKernelGGL(rows_prep_kernel<bf16>, dim3(gg), dim3(256), 0, st, g, ng, D, gsq, (bf16*)gc, p.Dp, metric);
   else
-    hipLaunchKernelGGL(rows_prep_kernel<float>, dim3(gg), dim3(256), 0, st, g, ng, D, gsq, (float*)gc, p.Dp, metric);
+    launch_rows_prep(dtype, g, ng, D, gsq, gc, p.Dp, metric, st);
   {
     long long b = (N + 255) / 256;
     if (b > 256) b = 256;
@@ -2234,34 +2007,31 @@ extern "C" int artsbir_pairwise_l2_topk(int dtype, int metric, const float* q, i
   hipLaunchKernelGGL(knn_init_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, qsq, ext, Q, rel, metric,
                      dpos_in, qeps, dpos, cnt, unc + 2 * p.unc_cap);
   if (positives)
-    hipLaunchKernelGGL(knn_band_kernel, dim3(gq), dim3(256), 0, st, q, g, positives, g_base, N, qsq, 0.f, Q, D, rel, dpos,
-                       lo, hi, metric, qeps);
+    hipLaunchKernelGGL(knn_band_kernel, dim3(gq), dim3(256), 0, st, q, g, positives, g_base, N, Q, D, dpos, lo, hi, metric,
+                       qeps);
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (g_scan_prof && hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess) {
     (void)hipEventRecord(ev0, st);
     g_scan_ev.emplace_back(ev0, ev1);
   }
   KnnScanArgs a;
-  a.q = qc; a.g = gc; a.qsq = qsq; a.gsq = gsq; a.gsq_max = 0.f; a.gsq_max_p = reinterpret_cast<const float*>(ext);
+  a.q = qc; a.g = gc; a.qsq = qsq; a.gsq = gsq;
+  a.gsq_max_p = reinterpret_cast<const float*>(ext);
   // the shared k-th bound and its histogram read the k-th entry of a KT-item list: off for large k
-  a.thr0 = nullptr; a.kb = (p.v2 && kb_on && !p.large) ? kbuf : nullptr; a.kq = k;
-  a.hist = a.kb && hist_on ? hist : nullptr; a.hbase = a.hist ? hbase : nullptr; a.rel = rel; a.Nq = Q; a.Ng = ng; a.D = p.Dp;
-  a.tiles_per_chunk = p.tpc;
-  a.nchunks = p.nchunks;
+  a.kb = (p.v2 && kb_on && !p.large) ? kbuf : nullptr;
+  a.hist = a.kb && hist_on ? hist : nullptr;
+  a.hbase = a.hist ? hbase : nullptr;
+  a.kq = k; a.rel = rel;
+  a.Nq = Q; a.Ng = ng; a.D = p.Dp;
+  a.tiles_per_chunk = p.tpc; a.nchunks = p.nchunks;  // the v1 scan's chunks are tiles_per_chunk x 128 rows as well
   a.lo = positives ? lo : nullptr; a.hi = positives ? hi : nullptr;
-  a.cnt = cnt; a.unc = unc; a.unc_cap = p.unc_cap; a.cand_d = cand_d; a.cand_i = cand_i; a.col_n = nullptr; a.col_i = nullptr; a.col_cap = 0;
+  a.cnt = cnt; a.unc = unc; a.unc_cap = p.unc_cap;
+  a.cand_d = cand_d; a.cand_i = cand_i;
   if (p.v2) {
-    const unsigned grid = (unsigned)(p.nchunks * ((Q + 255) / 256));
-    const int sstat = knn_stat_on() ? 1 : 0;
-    knn_scan_v2_launch(p.Dp, grid, a, sstat, st);
+    launch_scan_v2<0>(p.Dp, a, knn_stat_on() ? 1 : 0, st);
     set_last_kernel("knn_scan_v2_kernel");
   } else {
-    // knn_scan_kernel's chunks are tiles_per_chunk x 128 rows as well
-    const unsigned grid = (unsigned)(p.nchunks * ((Q + 127) / 128));
-    if (dtype == ARTSBIR_DT_BF16)
-      hipLaunchKernelGGL(knn_scan_kernel<bf16>, dim3(grid), dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL(knn_scan_kernel<float>, dim3(grid), dim3(256), 0, st, a);
+    launch_scan_v1<0>(dtype, a, st);
     set_last_kernel("knn_scan_kernel");
   }
   ARTSBIR_CHECK_LAUNCH("pairwise_l2_topk scan");
@@ -2283,18 +2053,16 @@ extern "C" int artsbir_pairwise_l2_topk(int dtype, int metric, const float* q, i
       c.thr0 = cthr; c.kb = nullptr; c.hist = nullptr; c.hbase = nullptr; c.lo = nullptr; c.hi = nullptr;
       c.col_n = col_n; c.col_i = col_i; c.col_cap = p.cand_cap;
       if (p.v2)
-        knn_scan_v2_collect_launch(p.Dp, (unsigned)(p.nchunks * ((Q + 255) / 256)), c, st);
-      else if (dtype == ARTSBIR_DT_BF16)
-        hipLaunchKernelGGL((knn_scan_kernel<bf16, 1>), dim3((unsigned)(p.nchunks * ((Q + 127) / 128))), dim3(256), 0, st, c);
+        launch_scan_v2<1>(p.Dp, c, 0, st);
       else
-        hipLaunchKernelGGL((knn_scan_kernel<float, 1>), dim3((unsigned)(p.nchunks * ((Q + 127) / 128))), dim3(256), 0, st, c);
+        launch_scan_v1<1>(dtype, c, st);
     }
     hipLaunchKernelGGL(knn_lk_select_kernel, dim3(Q), dim3(512), 0, st, q, g, D, ng, k, metric, g_base, col_n, col_i,
                        p.cand_cap, p.allrows, out_idx, out_dist, flag);
-  } else if (!launch_merge_wave(Q, st, q, g, D, p.nchunks, cand_d, cand_i, qsq, 0.f, rel, g_base, k, out_idx, out_dist,
-                                flag, metric, qeps, N))
-    hipLaunchKernelGGL(knn_merge_kernel, dim3(Q), dim3(256), sh, st, q, g, D, p.nchunks, cand_d, cand_i, qsq, 0.f, rel,
-                       g_base, k, out_idx, out_dist, flag, metric, qeps, N);
+  } else if (!launch_merge_wave(Q, st, q, g, D, p.nchunks, cand_d, cand_i, g_base, k, out_idx, out_dist, flag, metric,
+                                qeps, N))
+    hipLaunchKernelGGL(knn_merge_kernel, dim3(Q), dim3(256), sh, st, q, g, D, p.nchunks, cand_d, cand_i, g_base, k,
+                       out_idx, out_dist, flag, metric, qeps, N);
   if (positives) {
     hipLaunchKernelGGL(knn_uncertain_kernel, dim3(1024), dim3(256), 0, st, q, g, D, unc, p.unc_cap, dpos, positives,
                        g_base, cnt, metric);
@@ -2318,6 +2086,86 @@ extern "C" int artsbir_pairwise_l2_topk(int dtype, int metric, const float* q, i
     return -2;
   }
   ARTSBIR_CHECK_LAUNCH("pairwise_l2_topk");
+  return 0;
+}
+
+// ------------------------------------------------- the small entry points
+// single stages for tests, tools and the sharded path, the diagnostics and the
+// two test hooks
+extern "C" int artsbir_pairwise_l2(const float* x1, long long n1, const float* x2, long long n2, int D, float eps,
+                                   float* out, void* stream) {
+  if (!(n1 == n2 || n1 == 1 || n2 == 1)) { set_error("pairwise_l2: shapes %lld vs %lld", n1, n2); return -1; }
+  const long long n = n1 > n2 ? n1 : n2;
+  long long grid = (n + 3) / 4;
+  if (grid > 65536) grid = 65536;
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL(pairwise_l2_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x1, n1, x2, n2, D, eps, out);
+  ARTSBIR_CHECK_LAUNCH("pairwise_l2");
+  return 0;
+}
+
+extern "C" int artsbir_rows_prep(int dtype, const float* x, int n, int D, float* sq, void* xc, int ldc, void* stream) {
+  if (n <= 0) return 0;
+  if (ldc < D) ldc = D;
+  launch_rows_prep(dtype, x, n, D, sq, xc, ldc, 0, (hipStream_t)stream);
+  ARTSBIR_CHECK_LAUNCH("rows_prep");
+  return 0;
+}
+
+extern "C" int artsbir_rows_prep_aug(const float* x, int n, int D, int Dp, float* sq, void* xa, void* stream) {
+  if (Dp < D || Dp % 16) { set_error("rows_prep_aug: Dp=%d must be >= D=%d and a multiple of 16", Dp, D); return -1; }
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(rows_prep_aug_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, n, D, Dp,
+                     sq, (bf16*)xa, 0);
+  ARTSBIR_CHECK_LAUNCH("rows_prep_aug");
+  return 0;
+}
+
+extern "C" int artsbir_knn_candidates_per_query(int ng, int tiles_per_chunk) {
+  const int tiles = (ng + 127) / 128;
+  const int nchunks = (tiles + tiles_per_chunk - 1) / tiles_per_chunk;
+  return nchunks * KT;
+}
+
+extern "C" int artsbir_knn_scan(int dtype, const void* qc, const void* gc, const float* qsq, const float* gsq, int nq,
+                                int ng, int D, int tiles_per_chunk, const float* lo, const float* hi, int* cnt, int* unc,
+                                int unc_cap, float* cand_d, int* cand_i, void* stream) {
+  const int EPC = dtype == ARTSBIR_DT_BF16 ? 8 : 4;
+  if (D % (8 * EPC)) { set_error("knn_scan: D=%d must be a multiple of %d", D, 8 * EPC); return -1; }
+  if (nq <= 0 || ng <= 0) return 0;
+  KnnScanArgs a;
+  a.q = qc; a.g = gc; a.qsq = qsq; a.gsq = gsq;
+  a.Nq = nq; a.D = D;
+  a.chunks(ng, tiles_per_chunk);
+  a.lo = lo; a.hi = hi; a.cnt = cnt; a.unc = unc; a.unc_cap = unc_cap;
+  a.cand_d = cand_d; a.cand_i = cand_i;
+  launch_scan_v1<0>(dtype, a, (hipStream_t)stream);
+  ARTSBIR_CHECK_LAUNCH("knn_scan");
+  return 0;
+}
+
+extern "C" int artsbir_knn_scan_aug_supported(int Dp) { return Dp == 64 || Dp == 128 || Dp == 256 || Dp == 512; }
+
+extern "C" int artsbir_knn_scan_aug(const void* qc, const void* ga, const float* qsq, float gsq_max, int nq, int ng,
+                                    int Dp, int tiles_per_chunk, const float* thr0, unsigned* kbound, int k, float rel,
+                                    const float* lo, const float* hi, int* cnt, int* unc, int unc_cap, float* cand_d,
+                                    int* cand_i, void* stream) {
+  if (!artsbir_knn_scan_aug_supported(Dp)) { set_error("knn_scan_aug: Dp=%d not in {64,128,256,512}", Dp); return -1; }
+  if (tiles_per_chunk <= 0 || (long long)tiles_per_chunk * 128 * (2LL * Dp + 16) > 0x7fffffffLL) {
+    set_error("knn_scan_aug: tiles_per_chunk=%d out of range", tiles_per_chunk);
+    return -1;
+  }
+  if (kbound && (k < 1 || k > KT)) { set_error("knn_scan_aug: k=%d must be in 1..%d with a shared bound", k, KT); return -1; }
+  if (nq <= 0 || ng <= 0) return 0;
+  KnnScanArgs a;
+  a.q = qc; a.g = ga; a.qsq = qsq; a.gsq_max = gsq_max;
+  a.thr0 = thr0; a.kb = kbound; a.kq = k; a.rel = rel;
+  a.Nq = nq; a.D = Dp;
+  a.chunks(ng, tiles_per_chunk);
+  a.lo = lo; a.hi = hi; a.cnt = cnt; a.unc = unc; a.unc_cap = unc_cap;
+  a.cand_d = cand_d; a.cand_i = cand_i;
+  launch_scan_v2<0>(Dp, a, 0, (hipStream_t)stream);
+  ARTSBIR_CHECK_LAUNCH("knn_scan_aug");
   return 0;
 }
 
@@ -2347,6 +2195,34 @@ extern "C" int artsbir_positive_key(int metric, const float* q, int Q, const flo
   return 0;
 }
 
+extern "C" int artsbir_knn_exact_keys(int metric, const float* q, int Q, const float* g, long long N, int D,
+                                      double* out, void* stream) {
+  if (metric != 0 && metric != 1) { set_error("knn_exact_keys: metric %d (0 = euclidean, 1 = cosine)", metric); return -1; }
+  if (Q < 0 || N < 0 || D < 1) { set_error("knn_exact_keys: Q=%d N=%lld D=%d", Q, N, D); return -1; }
+  if (Q == 0 || N == 0) return 0;
+  const long long gx = std::min<long long>((N + 3) / 4, 16384);
+  hipLaunchKernelGGL(knn_exact_keys_kernel, dim3((unsigned)gx, (unsigned)std::min(Q, 4096)), dim3(256), 0,
+                     (hipStream_t)stream, q, Q, g, N, D, metric, out);
+  ARTSBIR_CHECK_LAUNCH("knn_exact_keys");
+  return 0;
+}
+
+// capacity of the uncertain-item queue of artsbir_pairwise_l2_topk (default
+// 2^20); a small value forces the exhaustive recount path (tests).  Returns the old one.
+extern "C" int artsbir_knn_set_unc_cap(int cap) {
+  const int old = g_topk_unc_cap;
+  if (cap > 0) g_topk_unc_cap = cap;
+  return old;
+}
+
+// upper limit of the candidate capacity C = 2 k + 2048 of the large-k path (default
+// LK_SORT: no limit); a small value forces the exhaustive fallback (tests).  Returns the old one.
+extern "C" int artsbir_knn_set_cand_cap(int cap) {
+  const int old = g_topk_cand_cap;
+  if (cap > 0) g_topk_cand_cap = cap < LK_SORT ? cap : LK_SORT;
+  return old;
+}
+
 // scan-kernel timing of artsbir_pairwise_l2_topk: on = 1 starts collecting (and
 // drops what was collected), 0 stops; read waits for the recorded events and
 // returns the summed scan time (ms) and the number of scans.
@@ -2373,20 +2249,13 @@ extern "C" int artsbir_scan_profile_read(double* total_ms, int* count) {
   return 0;
 }
 
-// capacity of the uncertain-item queue of artsbir_pairwise_l2_topk (default
-// 2^20); a small value forces the exhaustive recount path (tests).  Returns the old one.
-extern "C" int artsbir_knn_set_unc_cap(int cap) {
-  const int old = g_topk_unc_cap;
-  if (cap > 0) g_topk_unc_cap = cap;
-  return old;
-}
-
-// upper limit of the candidate capacity C = 2 k + 2048 of the large-k path (default
-// LK_SORT: no limit); a small value forces the exhaustive fallback (tests).  Returns the old one.
-extern "C" int artsbir_knn_set_cand_cap(int cap) {
-  const int old = g_topk_cand_cap;
-  if (cap > 0) g_topk_cand_cap = cap < LK_SORT ? cap : LK_SORT;
-  return old;
+extern "C" int artsbir_knn_stat_read(unsigned long long* out4, int reset) {
+  if (hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_knn_stat), sizeof(unsigned long long) * 4) != hipSuccess) return -1;
+  if (reset) {
+    static const unsigned long long z[4] = {0, 0, 0, 0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_knn_stat), z, sizeof(z)) != hipSuccess) return -1;
+  }
+  return 0;
 }
 
 extern "C" int artsbir_knn_largek_stat_read(long long* out2, int reset) {
@@ -2398,17 +2267,5 @@ extern "C" int artsbir_knn_largek_stat_read(long long* out2, int reset) {
     static const unsigned long long z[2] = {0, 0};
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_knn_lk_stat), z, sizeof(z)) != hipSuccess) return -1;
   }
-  return 0;
-}
-
-extern "C" int artsbir_knn_exact_keys(int metric, const float* q, int Q, const float* g, long long N, int D,
-                                      double* out, void* stream) {
-  if (metric != 0 && metric != 1) { set_error("knn_exact_keys: metric %d (0 = euclidean, 1 = cosine)", metric); return -1; }
-  if (Q < 0 || N < 0 || D < 1) { set_error("knn_exact_keys: Q=%d N=%lld D=%d", Q, N, D); return -1; }
-  if (Q == 0 || N == 0) return 0;
-  const long long gx = std::min<long long>((N + 3) / 4, 16384);
-  hipLaunchKernelGGL(knn_exact_keys_kernel, dim3((unsigned)gx, (unsigned)std::min(Q, 4096)), dim3(256), 0,
-                     (hipStream_t)stream, q, Q, g, N, D, metric, out);
-  ARTSBIR_CHECK_LAUNCH("knn_exact_keys");
   return 0;
 }

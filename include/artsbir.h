@@ -510,13 +510,6 @@ int artsbir_pairwise_l2(const float* x1, long long n1, const float* x2, long lon
 /* sq[i] = ||x[i]||^2 (f32) and, if xc != NULL, the compute-dtype copy of x with
  * rows zero-padded to ldc columns (the MFMA scan needs D % 64 == 0). */
 int artsbir_rows_prep(int dtype, const float* x, int n, int D, float* sq, void* xc, int ldc, void* stream);
-/* exact f64 distance to the positive (rows whose positive lies in [g_base, g_base+n_g)),
- * else dpos taken as given (<0: no positive); rank band lo/hi = dpos^2 -/+ eps(rel). */
-int artsbir_knn_band(const float* q, const float* g, const long long* pos, long long g_base, long long n_g,
-                     const float* qsq, float gsq_max, int nq, int D, float rel, double* dpos, float* lo,
-                     float* hi, void* stream);
-int artsbir_knn_band_from_dpos(const double* dpos, const float* qsq, float gsq_max, int nq, float rel,
-                               float* lo, float* hi, void* stream);
 /* candidates per query of artsbir_knn_scan for a gallery of ng rows. */
 int artsbir_knn_candidates_per_query(int ng, int tiles_per_chunk);
 /* fused MFMA scan: per (query, gallery chunk) the 16 smallest approximate squared
@@ -544,16 +537,6 @@ int artsbir_knn_scan_aug(const void* qc, const void* ga, const float* qsq, float
                          int Dp, int tiles_per_chunk, const float* thr0, unsigned* kbound, int k, float rel,
                          const float* lo, const float* hi, int* cnt, int* unc, int unc_cap, float* cand_d,
                          int* cand_i, void* stream);
-/* exact f64 top-k by (distance, index) from the candidates; flag[q] = 1 when a
- * chunk list could have dropped a true top-k item (caller re-runs exhaustively). */
-int artsbir_knn_merge(const float* q, const float* g, int D, int nq, int nchunks, const float* cand_d,
-                      const int* cand_i, const float* qsq, float gsq_max, float rel, long long g_base, int k,
-                      long long* out_i, double* out_d, int* flag, void* stream);
-/* cnt[q] += #{uncertain g : d < dpos or (d == dpos and g_base+g < pos)} (exact f64). */
-int artsbir_knn_uncertain(const float* q, const float* g, int D, const int* unc, int unc_cap,
-                          const double* dpos, const long long* pos, long long g_base, int* cnt, void* stream);
-/* out[i] = exact f64 ||q - g_i + 1e-6|| for all i (fallback / tiny galleries). */
-int artsbir_knn_exact_all(const float* q, const float* g, int D, int n, double* out, void* stream);
 
 /* ONE-CALL exact retrieval (replaces the per-query loop of inference.py:30-69:
  * utils.euclidean_distance / utils.cosine_distance of [1,D] vs the [N,D]
@@ -599,7 +582,7 @@ int artsbir_knn_set_cand_cap(int cap);
 int artsbir_knn_largek_stat_read(long long* out2, int reset);
 /* out[q][i] = exact f64 key (metric 0 / 1 as artsbir_pairwise_l2_topk) of query q
  * and gallery row i, out is [Q][N]: the plain path for k > 1024 (sort on the
- * caller's side) and the metric-aware, multi-query form of artsbir_knn_exact_all. */
+ * caller's side). */
 int artsbir_knn_exact_keys(int metric, const float* q, int Q, const float* g, long long N, int D, double* out,
                            void* stream);
 /* HIP-event timing of the scan kernel inside artsbir_pairwise_l2_topk (profiling):

@@ -63,7 +63,9 @@ def _check(out, ri, rd, rr=None, pos=None, atol=0.0):
 # (5000, 128, 32, 1024): 40 tiles x 16 list items < k, no cut exists (exhaustive
 # kernel); (300, ...): N <= C, sorted whole; D = 768 takes knn_scan_kernel in bf16 too
 SHAPES = [(20000, 64, 64, 65), (20000, 512, 48, 100), (20000, 64, 64, 1000), (5000, 128, 32, 1024),
-          (300, 128, 20, 200), (4000, 768, 24, 100)]
+          (300, 128, 20, 200), (4000, 768, 24, 100),
+          # the collect-mode v2 scan at Dp = 128 and 256 (the cases above reach it at Dp = 64 and 512 only)
+          (6000, 128, 24, 100), (6000, 256, 24, 100)]
 
 
 @pytest.mark.parametrize("metric", ["euclidean", "cosine"])
