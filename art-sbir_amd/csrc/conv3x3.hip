@@ -209,24 +209,48 @@ bool sconv_launch(const PgArgs& a, hipStream_t st) {
 // and the layer-1 conv2 (models.py:200-201, 56x56), forward and data gradient
 // with the fused BN-backward reduction.
 //
-// An output tile is TR x TC pixels of one image (all Cout channels).  Its
-// input halo of (TR+2) x (TC+2) pixels is brought into LDS ONCE by LDS-DMA and
-// all nine taps read it there (sconv re-reads every input pixel nine times
-// through L1/L2 as fragment-shaped loads).  One loader wave streams the halo
-// of the block's next tile into the second of two halo buffers while four
-// compute waves run the MFMAs of the current one out of the first; the filter
+// An output tile is TR x TC pixels of one image (all Cout channels): 16 x 16
+// where the image splits evenly and three such halos fit the LDS beside the
+// filters, else 8 x 16.  Its input halo of (TR+2) x (TC+2) pixels is brought
+// into LDS ONCE by LDS-DMA and all nine taps read it there (sconv re-reads every
+// input pixel nine times through L1/L2 as fragment-shaped loads); the filter
 // bank stays in LDS for the whole persistent block.
+//
+// Eight compute waves, two per SIMD, as two groups of four that take the
+// block's tiles alternately, half a tile apart.  Between two workgroup barriers
+// one group runs the MFMAs of tile j while the other runs the epilogue of tile
+// j - 1 (BN-backward arithmetic, 16-B stores) and issues the halo DMA of tile
+// j + 2, so a SIMD's matrix pipe has work while its other wave stores.  There
+// is no loader wave: the four waves of the group in its epilogue half share the
+// DMA instructions, and each waits for its own (vmcnt(0)) before the barrier
+// that ends its next MFMA half — the barrier after which the other group reads
+// that halo.  Three halo buffers: tile j in buffer j % 3; the buffer of tile j
+// is refilled (tile j + 3) by the group that read it, after the barrier that
+// ends its MFMA half.  Every wave passes n + 1 barriers for the block's n tiles
+// (group 1 starts one barrier late; the group without a tile in the last half
+// passes one more at the end).
 //
 // Halo LDS image: 1-KB blocks of PB pixels x CPT 16-B channel chunks, chunk
 // major inside a block (lane l of a DMA instruction fills chunk l / PB of
 // pixel l % PB, so one instruction reads PB whole pixels = 1 KB of contiguous
 // NHWC input).  A B fragment read (16 consecutive halo pixels of one tile row,
 // one chunk per lane quad) then hits 16 distinct 16-B bank slots in every
-// ds_read_b128 lane group, for every tap offset.
+// ds_read_b128 lane group, for every tap offset; the filter reads keep sconv's
+// pg_perm / sc_sw image (SQ_LDS_BANK_CONFLICT 0 in every instance).
 //
-// The BN-backward operand of the epilogue (y of the BN before the ReLU) and
-// the per-channel parameters are loaded into registers before the MFMAs, so
-// their latency hides behind them.
+// The BN-backward operand of the epilogue (y of the BN before the ReLU) is
+// loaded one tile of the group ahead, after the previous epilogue.  The sums (BN
+// statistics, or the BN-backward reduction) stay in registers, one partial per
+// lane, across all tiles of a segment; a wave reduces them over its 16 pixel
+// lanes and adds them to its replica slot when the segment changes and at the
+// end — a few times per launch, not once per tile — so the tile loop has no LDS
+// accumulator, no counter and no flush.  (The deterministic mode takes no sums
+// from this kernel: it launches it without them.)
+//
+// With 64 -> 64 channels the filters take 72 KB, which leaves the LDS for three
+// 8 x 16 halos and no more: neither a second workgroup per CU, nor a tile whose
+// rows are 56 wide (2 x 56 needs 29 KB per halo, 87 KB for three), nor four
+// pixel fragments per wave (a 16 x 16 halo is 41 KB) fits.
 // ---------------------------------------------------------------------------
 #define HC_MAXSEG 4
 template <int C>
@@ -236,68 +260,59 @@ __device__ __forceinline__ int hc_addr(int q, int c) {
   return ((q >> PBL) << 10) + c * (PB * 16) + ((q & (PB - 1)) << 4);
 }
 
-template <int C, int COUT, int TR, int TC>
+template <int C, int COUT, int TR, int TC, bool BNB>
 struct HcGeom {
-  static constexpr int NWC = 4;                    // compute waves
+  static constexpr int NWG = 4;                    // compute waves per group
   static constexpr int CPT = C / 8, PB = 64 / CPT;
-  static constexpr int NKK = 9 * C / 32;           // 32-k MFMA steps
+  static constexpr int NKK = 9 * C / 32;
   static constexpr int MTC = COUT / 16, NP = MTC / 2;
-  static constexpr int TCB = TC / 16;              // 16-pixel MFMA tiles per tile row
-  static constexpr int NTP = TR * TCB / NWC;       // MFMA pixel tiles per compute wave
+  static constexpr int TCB = TC / 16;
+  static constexpr int NTP = TR * TCB / NWG;       // MFMA pixel tiles per wave
   static constexpr int HW = TC + 2, NQ = HW * (TR + 2);
-  static constexpr int NB = (NQ + PB - 1) / PB;    // 1-KB halo blocks
+  static constexpr int NB = (NQ + PB - 1) / PB;
   static constexpr int HB = NB * 1024;
-  static constexpr int WB = NKK * COUT * 64;       // filter image
-  static constexpr int PRM = HC_MAXSEG * 4 * COUT * 4;  // BN-backward parameters per segment
-  static constexpr int FIX = WB + PRM + pg_red_bytes<COUT>();
-  // halo buffers: three (two tiles in flight behind the one being computed)
-  // where that fits and keeps the workgroups per CU, else two; NB <= 31 so the
-  // loader's counted vmcnt(NB) fits the 6-bit field
-  static constexpr bool THREE = FIX + 3 * HB <= 160 * 1024 && (160 * 1024) / (FIX + 3 * HB) ==
-                                (160 * 1024) / (FIX + 2 * HB) && NB <= 31;
-  static constexpr int NBUF = THREE ? 3 : 2;
-  static constexpr int LDS = WB + NBUF * HB + PRM + pg_red_bytes<COUT>();
-  // waves per SIMD the registers must allow for every workgroup the LDS admits
-  // to fit on a CU (5 waves each: 4 compute + the loader), at most 3 (168
-  // VGPRs: below that the tiles spill).  Without it the 32 -> 32 stem tile
-  // (216 VGPRs, LDS for two workgroups) ran one workgroup per CU: one compute
-  // wave per SIMD.
-  static constexpr int WPB = (160 * 1024) / LDS > 4 ? 4 : (160 * 1024) / LDS;
-  static constexpr int WPE = (5 * WPB + 3) / 4 > 3 ? 3 : (5 * WPB + 3) / 4;
+  static constexpr int WB = NKK * COUT * 64;
+  // BN-backward parameters per segment: an LDS table, or, where the table is what
+  // would not fit (64 -> 32 at 16 x 16: 159 KB of filters and halos), the lane's
+  // own 8 channels in registers, reloaded when the segment changes
+  static constexpr int PTAB = BNB ? HC_MAXSEG * 4 * COUT * 4 : 0;
+  static constexpr bool PREG = BNB && NP == 1 && WB + 3 * HB + PTAB > 160 * 1024;
+  static constexpr int PRM = PREG ? 0 : PTAB;
+  static constexpr int LDS = WB + 3 * HB + PRM;
+  static constexpr bool FITS = LDS <= 160 * 1024;
 };
 
 template <int C, int COUT, int TR, int TC, bool BNB>
-__global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(HcGeom<C, COUT, TR, TC>::WPE)))
-hconv_kernel(PgArgs a, int ntiles) {
-  using Gm = HcGeom<C, COUT, TR, TC>;
-  constexpr int NWC = Gm::NWC, PB = Gm::PB, NKK = Gm::NKK, MTC = Gm::MTC, NP = Gm::NP;
+__global__ void __launch_bounds__(512) hconv_kernel(PgArgs a, int ntiles) {
+  using Gm = HcGeom<C, COUT, TR, TC, BNB>;
+  constexpr int NWG = Gm::NWG, PB = Gm::PB, NKK = Gm::NKK, MTC = Gm::MTC, NP = Gm::NP;
   constexpr int TCB = Gm::TCB, NTP = Gm::NTP, HW = Gm::HW, NQ = Gm::NQ, NB = Gm::NB, HB = Gm::HB;
-  constexpr int WB = Gm::WB, NBUF = Gm::NBUF;
+  constexpr int WB = Gm::WB;
   static_assert(C % 32 == 0 && COUT % 32 == 0 && TC % 16 == 0, "tile shape");
-  static_assert(NTP * NWC == TR * TCB, "pixel tiles per wave");
-  static_assert(Gm::LDS <= 160 * 1024, "LDS");
+  static_assert(NTP * NWG == TR * TCB, "pixel tiles per wave");
+  static_assert(Gm::FITS, "LDS");
   __shared__ __attribute__((aligned(16))) char smem[Gm::LDS];
-  float* prm = reinterpret_cast<float*>(smem + WB + NBUF * HB);  // [seg][istd, mean, mask scale, mask beta][COUT]
-  float* red = reinterpret_cast<float*>(smem + WB + NBUF * HB + Gm::PRM);
-  int* red_cnt = reinterpret_cast<int*>(smem + WB + NBUF * HB + Gm::PRM + 6 * COUT * 4);
+  float* prm = reinterpret_cast<float*>(smem + WB + 3 * HB);  // [seg][istd, mean, mask scale, mask beta][COUT]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int grp = wid >> 2, wg = wid & 3;
   const int fr = lane & 15, fq = lane >> 4;
   const int G = gridDim.x;
   const int ntw = (a.Wo + TC - 1) / TC, nth = (a.Ho + TR - 1) / TR;
   const int HoWo = a.Ho * a.Wo;
   const bool sums = a.stats != nullptr || BNB;
+  const int n = (ntiles - (int)blockIdx.x + G - 1) / G;  // tiles of this block (the grid is at most ntiles)
 
-  // halo of tile t -> buffer buf (loader wave)
-  auto issue_halo = [&](int t, int buf) {
+  // this wave's share of the halo DMA of the block's j-th tile -> buffer j % 3
+  auto issue_halo = [&](int j) {
+    const int t = blockIdx.x + j * G;
     const int img = t / (nth * ntw), rem = t - img * (nth * ntw);
     const int h0 = (rem / ntw) * TR, w0 = (rem - (rem / ntw) * ntw) * TC;
     const __amdgpu_buffer_rsrc_t xr =
         pg_rsrc(reinterpret_cast<const bf16*>(a.x) + (long long)img * a.sN, (a.x_elems - (long long)img * a.sN) * 2);
-    char* hb = smem + WB + buf * HB;
+    char* hb = smem + WB + (j % 3) * HB;
     const int c = lane / PB, ql = lane - c * PB;
-#pragma unroll 4
-    for (int b = 0; b < NB; ++b) {
+    for (int b = wg; b < NB; b += NWG) {
       const int q = b * PB + ql;
       const int hr = q / HW, hc = q - (q / HW) * HW;
       const int ih = h0 - 1 + hr, iw = w0 - 1 + hc;
@@ -306,141 +321,168 @@ hconv_kernel(PgArgs a, int ntiles) {
     }
   };
 
-  if (wid == NWC) {
-    if ((int)blockIdx.x < ntiles) issue_halo(blockIdx.x, 0);
-    if (NBUF == 3 && (int)blockIdx.x + G < ntiles) issue_halo(blockIdx.x + G, 1);
-  } else {
-    if (sums) {
-      for (int i = tid; i < 6 * COUT; i += 64 * NWC) red[i] = 0.f;
-      if (tid == 0) *red_cnt = 0;
-    }
-    if constexpr (BNB) {
-      const int nsg = a.seg_m > 0 ? (int)(a.M / a.seg_m) : 1;
-      for (int i = tid; i < nsg * 4 * COUT; i += 64 * NWC) {
-        const int sg = i / (4 * COUT), r = (i / COUT) & 3, ch = i % COUT;
-        const float* src = r == 0 ? a.bnb_istd[0] : r == 1 ? a.bnb_mean[0]
-                         : r == 2 ? a.bnb_mbn + 2 * a.Cout : a.bnb_mbn + 3 * a.Cout;
-        prm[i] = src[sg * a.bnb_pstride + ch];
-      }
-    }
-    // filters -> LDS (sconv's image: block kk holds COUT rows of 64 B)
-    for (int i = tid; i < NKK * COUT * 4; i += 64 * NWC) {
-      const int kk = i / (COUT * 4), rem = i - kk * COUT * 4;
-      const int rho = rem >> 2, c = rem & 3;
-      const uint4 v =
-          *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(a.w) + (long long)pg_perm(rho) * a.K + kk * 32 + c * 8);
-      *reinterpret_cast<uint4*>(smem + (kk * COUT + rho) * 64 + ((c ^ sc_sw(rho)) << 4)) = v;
+  if (grp < n) issue_halo(grp);
+  if constexpr (BNB && !Gm::PREG) {
+    const int nsg = a.seg_m > 0 ? (int)(a.M / a.seg_m) : 1;
+    for (int i = tid; i < nsg * 4 * COUT; i += 128 * NWG) {
+      const int sg = i / (4 * COUT), r = (i / COUT) & 3, ch = i % COUT;
+      const float* src = r == 0 ? a.bnb_istd[0] : r == 1 ? a.bnb_mean[0]
+                       : r == 2 ? a.bnb_mbn + 2 * a.Cout : a.bnb_mbn + 3 * a.Cout;
+      prm[i] = src[sg * a.bnb_pstride + ch];
     }
   }
+  // filters -> LDS (sconv's image: block kk holds COUT rows of 64 B)
+  for (int i = tid; i < NKK * COUT * 4; i += 128 * NWG) {
+    const int kk = i / (COUT * 4), rem = i - kk * COUT * 4;
+    const int rho = rem >> 2, c = rem & 3;
+    const uint4 v =
+        *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(a.w) + (long long)pg_perm(rho) * a.K + kk * 32 + c * 8);
+    *reinterpret_cast<uint4*>(smem + (kk * COUT + rho) * 64 + ((c ^ sc_sw(rho)) << 4)) = v;
+  }
+  vm_wait<0>();  // the first halos of both groups have landed before barrier 0
 
-  // the loader and the compute waves run separate loops with one barrier per
-  // tile each (a role branch inside one loop makes the compiler merge and copy
-  // the accumulators every tile)
-  if (wid == NWC) {
-    int k = 0;
-    for (int tile = blockIdx.x; tile < ntiles; tile += G, ++k) {
-      // this tile's halo has landed (with three buffers the next tile's, issued
-      // after it, may still be in flight: its NB DMAs are the newest)
-      if (NBUF == 3 && tile + G < ntiles) vm_wait<NB>();
-      else vm_wait<0>();
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      // the buffer of tile k-1, which every compute wave left before this barrier
-      if (tile + (NBUF - 1) * G < ntiles) issue_halo(tile + (NBUF - 1) * G, (k + NBUF - 1) % NBUF);
-    }
-    vm_wait<0>();
-    return;
-  }
-  // per MFMA pixel tile j of a tile: this lane's output pixel and its halo position
-  auto tile_px = [&](int tile, long long (&px)[NTP], bool (&pv)[NTP], int (&qb)[NTP]) {
+  // per MFMA pixel tile m of the block's j-th tile: this lane's output pixel and its halo position
+  auto tile_px = [&](int j, long long (&px)[NTP], bool (&pv)[NTP], int (&qb)[NTP]) {
+    const int tile = blockIdx.x + j * G;
     const int img = tile / (nth * ntw), rem = tile - img * (nth * ntw);
     const int h0 = (rem / ntw) * TR, w0 = (rem - (rem / ntw) * ntw) * TC;
     const long long pimg = (long long)img * HoWo;
 #pragma unroll
-    for (int j = 0; j < NTP; ++j) {
-      const int m = wid * NTP + j, row = m / TCB, cb = m - (m / TCB) * TCB;
+    for (int m = 0; m < NTP; ++m) {
+      const int mt = wg * NTP + m, row = mt / TCB, cb = mt - (mt / TCB) * TCB;
       const int oh = h0 + row, ow = w0 + cb * 16 + fr;
-      pv[j] = oh < a.Ho && ow < a.Wo;
-      px[j] = pv[j] ? pimg + oh * a.Wo + ow : pimg;
-      qb[j] = row * HW + cb * 16 + fr;
+      pv[m] = oh < a.Ho && ow < a.Wo;
+      px[m] = pv[m] ? pimg + oh * a.Wo + ow : pimg;
+      qb[m] = row * HW + cb * 16 + fr;
     }
     return pimg;
   };
-  // the BN-backward operand of a tile is loaded one tile ahead (issued after the
-  // previous tile's epilogue, consumed in this tile's), so its latency runs
-  // under the barrier and the MFMAs instead of in front of them
+  // the BN-backward operand of a tile is loaded one tile of the group ahead
+  // (issued after the previous epilogue), so its latency runs under the other
+  // group's half and this group's MFMAs
   Vec16<bf16> yp[NP][NTP];
-  auto load_yp = [&](const long long (&px)[NTP]) {
-#pragma unroll
-    for (int p = 0; p < NP; ++p)
-#pragma unroll
-      for (int j = 0; j < NTP; ++j)
-        yp[p][j] = ld16<bf16>(reinterpret_cast<const bf16*>(a.bnb_y[0]) + px[j] * a.ldy + 32 * p + 8 * fq);
-  };
-  if constexpr (BNB) {
-    if ((int)blockIdx.x < ntiles) {
-      long long px0[NTP];
-      bool pv0[NTP];
-      int qb0[NTP];
-      tile_px(blockIdx.x, px0, pv0, qb0);
-      load_yp(px0);
-    }
-  }
-  int k = 0;
-  for (int tile = blockIdx.x; tile < ntiles; tile += G, ++k) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();   // halo k visible; buffer (k-1) % NBUF and the statistics accumulator free
-    asm volatile("" ::: "memory");
+  auto load_yp = [&](int j) {
     long long px[NTP];
     bool pv[NTP];
     int qb[NTP];
-    const long long pimg = tile_px(tile, px, pv, qb);
+    tile_px(j, px, pv, qb);
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+      for (int m = 0; m < NTP; ++m)
+        yp[p][m] = ld16<bf16>(reinterpret_cast<const bf16*>(a.bnb_y[0]) + px[m] * a.ldy + 32 * p + 8 * fq);
+  };
+  if constexpr (BNB) {
+    if (grp < n) load_yp(grp);
+  }
+  // the sums carried across the tiles of a segment, and their flush
+  float cs1[NP][8], cs2[NP][8];
+#pragma unroll
+  for (int p = 0; p < NP; ++p)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { cs1[p][e] = 0.f; cs2[p][e] = 0.f; }
+  long long cseg = -1;
+  float preg[4][8];  // PREG: istd, mean, mask scale, mask beta of the lane's channels
+  const int slot = (int)((blockIdx.x * (2 * NWG) + wid) % ARTSBIR_NSLOT);
+  auto sums_flush = [&]() {
+    const long long so = cseg * a.seg_stride + (long long)slot * 2 * a.Cout;
+    float* dst = (BNB ? a.bnb_slots[0] : a.stats) + so;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      const int ch0 = 32 * p + 8 * fq;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { cs1[p][e] = dpp_row_sum(cs1[p][e]); cs2[p][e] = dpp_row_sum(cs2[p][e]); }
+      if (fr == 15 && !(a.dbg & 1)) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          atomicAdd(dst + ch0 + e, cs1[p][e]);
+          atomicAdd(dst + a.Cout + ch0 + e, cs2[p][e]);
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { cs1[p][e] = 0.f; cs2[p][e] = 0.f; }
+    }
+  };
+  auto barrier = [&]() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  };
+
+  if (grp == 1) {
+    barrier();  // barrier 0: group 0 starts tile 0
+    if (2 < n) issue_halo(2);
+  }
+  for (int j = grp; j < n; j += 2) {
+    barrier();  // barrier j: halo j visible
+    long long px[NTP];
+    bool pv[NTP];
+    int qb[NTP];
+    const long long pimg = tile_px(j, px, pv, qb);
     const long long wseg = a.seg_m > 0 ? pimg / a.seg_m : 0;
     // ---- MFMAs: filters (A) and halo (B) from LDS
-    const char* hb = smem + WB + (k % NBUF) * HB;
+    const char* hb = smem + WB + (j % 3) * HB;
     f32x4 acc[MTC][NTP];
 #pragma unroll
     for (int i = 0; i < MTC; ++i)
 #pragma unroll
-      for (int j = 0; j < NTP; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int m = 0; m < NTP; ++m) acc[i][m] = f32x4{0.f, 0.f, 0.f, 0.f};
     constexpr int KPT = C / 32;  // 32-k steps per tap
     // taps fully unrolled where the registers allow (no spills), else by rows
-    // (by rows also where the waves-per-SIMD bound leaves too few registers)
-    constexpr int TUN = ((NTP <= 2 || (C == 32 && MTC * NTP <= 8)) && !(Gm::WPE >= 3 && NTP > 2)) ? 9 : 3;
+    constexpr int TUN = (NTP <= 2 || (C == 32 && MTC * NTP <= 8)) ? 9 : 3;
 #pragma unroll TUN
     for (int t = 0; t < 9; ++t) {
       const int toff = (t / 3) * HW + (t % 3);
       int qa[NTP];
 #pragma unroll
-      for (int j = 0; j < NTP; ++j) qa[j] = qb[j] + toff;
+      for (int m = 0; m < NTP; ++m) qa[m] = qb[m] + toff;
 #pragma unroll
-    for (int h = 0; h < KPT; ++h) {
-      const int kk = t * KPT + h, c = h * 4 + fq;
-      uint4 af[MTC], bv[NTP];
+      for (int h = 0; h < KPT; ++h) {
+        const int kk = t * KPT + h, c = h * 4 + fq;
+        uint4 af[MTC], bv[NTP];
 #pragma unroll
-      for (int i = 0; i < MTC; ++i) {
-        const int rho = i * 16 + fr;
-        af[i] = *reinterpret_cast<const uint4*>(smem + (kk * COUT + rho) * 64 + ((fq ^ sc_sw(rho)) << 4));
+        for (int i = 0; i < MTC; ++i) {
+          const int rho = i * 16 + fr;
+          af[i] = *reinterpret_cast<const uint4*>(smem + (kk * COUT + rho) * 64 + ((fq ^ sc_sw(rho)) << 4));
+        }
+#pragma unroll
+        for (int m = 0; m < NTP; ++m) bv[m] = *reinterpret_cast<const uint4*>(hb + hc_addr<C>(qa[m], c));
+#pragma unroll
+        for (int i = 0; i < MTC; ++i)
+#pragma unroll
+          for (int m = 0; m < NTP; ++m)
+            acc[i][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(&af[i]),
+                                                                *reinterpret_cast<const bf16x8*>(&bv[m]), acc[i][m], 0, 0, 0);
       }
-#pragma unroll
-      for (int j = 0; j < NTP; ++j) bv[j] = *reinterpret_cast<const uint4*>(hb + hc_addr<C>(qa[j], c));
-#pragma unroll
-      for (int i = 0; i < MTC; ++i)
-#pragma unroll
-        for (int j = 0; j < NTP; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(&af[i]),
-                                                              *reinterpret_cast<const bf16x8*>(&bv[j]), acc[i][j], 0, 0, 0);
     }
-    }
+    // this wave's DMAs of halo j + 1 (issued in its previous epilogue half) have
+    // landed before the barrier after which the other group reads them
+    vm_wait<0>();
+    barrier();  // barrier j + 1: buffer j % 3 is free
+    if (j + 3 < n) issue_halo(j + 3);
     // ---- epilogue: BN statistics or the fused BN-backward reduction, bf16 stores
+    if (sums && wseg != cseg) {
+      if (cseg >= 0) sums_flush();
+      cseg = wseg;
+      if constexpr (Gm::PREG) {
+        const long long po = wseg * a.bnb_pstride + 8 * fq;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          preg[0][e] = a.bnb_istd[0][po + e];
+          preg[1][e] = a.bnb_mean[0][po + e];
+          preg[2][e] = a.bnb_mbn[2 * a.Cout + po + e];
+          preg[3][e] = a.bnb_mbn[3 * a.Cout + po + e];
+        }
+      }
+    }
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
       const int ch0 = 32 * p + 8 * fq;
-      float s1[8], s2[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
       float xa[8], xm[8], ms[8], mh[8];
-      if constexpr (BNB) {
+      if constexpr (Gm::PREG) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { xa[e] = preg[0][e]; xm[e] = preg[1][e]; ms[e] = preg[2][e]; mh[e] = preg[3][e]; }
+      } else if constexpr (BNB) {
         const float* pp = prm + wseg * 4 * COUT + ch0;
         loadf8v(pp, xa);
         loadf8v(pp + COUT, xm);
@@ -448,11 +490,11 @@ hconv_kernel(PgArgs a, int ntiles) {
         loadf8v(pp + 3 * COUT, mh);
       }
 #pragma unroll
-      for (int j = 0; j < NTP; ++j) {
+      for (int m = 0; m < NTP; ++m) {
         float v[8];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { v[r] = acc[2 * p][j][r]; v[4 + r] = acc[2 * p + 1][j][r]; }
-        if (pv[j]) {
+        for (int r = 0; r < 4; ++r) { v[r] = acc[2 * p][m][r]; v[4 + r] = acc[2 * p + 1][m][r]; }
+        if (pv[m]) {
           if constexpr (!BNB) {  // eval-mode conv + folded BN (+ ReLU): bias and activation here
             if (a.bias) {
 #pragma unroll
@@ -466,44 +508,31 @@ hconv_kernel(PgArgs a, int ntiles) {
           if constexpr (BNB) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-              const float yv = to_f(yp[p][j].v[e]);
+              const float yv = to_f(yp[p][m].v[e]);
               v[e] = (yv - xm[e]) * ms[e] + mh[e] > 0.f ? v[e] : 0.f;  // kind 1: target 0 is the ReLU's BN
-              s1[e] += v[e];
-              s2[e] += v[e] * ((yv - xm[e]) * xa[e]);
+              cs1[p][e] += v[e];
+              cs2[p][e] += v[e] * ((yv - xm[e]) * xa[e]);
             }
           } else if (sums) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { s1[e] += v[e]; s2[e] += v[e] * v[e]; }
+            for (int e = 0; e < 8; ++e) { cs1[p][e] += v[e]; cs2[p][e] += v[e] * v[e]; }
           }
           Vec16<bf16> o;
 #pragma unroll
           for (int e = 0; e < 8; ++e) o.v[e] = from_f<bf16>(v[e]);
-          st16<bf16>(reinterpret_cast<bf16*>(a.y) + px[j] * a.ldy + ch0, o);
-        }
-      }
-      if (sums) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { s1[e] = dpp_row_sum(s1[e]); s2[e] = dpp_row_sum(s2[e]); }
-        if (fr == 15) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            atomicAdd(red + ch0 + e, s1[e]);
-            atomicAdd(red + COUT + ch0 + e, s2[e]);
-          }
+          st16<bf16>(reinterpret_cast<bf16*>(a.y) + px[m] * a.ldy + ch0, o);
         }
       }
     }
     if constexpr (BNB) {
-      if (tile + G < ntiles) {
-        long long pxn[NTP];
-        bool pvn[NTP];
-        int qbn[NTP];
-        tile_px(tile + G, pxn, pvn, qbn);
-        load_yp(pxn);
-      }
+      if (j + 2 < n) load_yp(j + 2);
     }
-    if (sums) stats_flush<COUT>(red, red_cnt, NWC * (k + 1) - 1, a, 0, tile % ARTSBIR_NSLOT, lane, pimg, 1);
   }
+  // barrier n for the group that took no tile in the last half.  n = 3: group 0 (tiles 0, 2) passed
+  // barriers 0 1 2 3 in its loop, group 1 (tile 1) passed 0 before it and 1 2 in it and takes 3 here;
+  // n = 4: group 1 (tiles 1, 3) passed 0, then 1 2 3 4, group 0 (tiles 0, 2) passed 0 1 2 3 and takes 4 here
+  if (((n + grp) & 1) == 0) barrier();
+  if (sums && cseg >= 0) sums_flush();
 }
 
 // shapes the halo-tiled kernel takes
@@ -521,12 +550,20 @@ static bool hconv_ok(const PgArgs& a) {
   return nt < 0x7fffffffLL;
 }
 
+// persistent grid: one workgroup of 512 per CU, or as many as the LDS and the registers admit
 template <int C, int COUT, int TR, int TC, bool BNB>
 static void hconv_go(const PgArgs& a, hipStream_t st) {
-  using Gm = HcGeom<C, COUT, TR, TC>;
+  using Gm = HcGeom<C, COUT, TR, TC, BNB>;
   const int ntiles = (int)((a.M / ((long long)a.Ho * a.Wo)) * ((a.Ho + TR - 1) / TR) * ((a.Wo + TC - 1) / TC));
-  int per_cu = (160 * 1024) / Gm::LDS;
-  if (per_cu > 4) per_cu = 4;
+  static const int per_cu = [] {
+    int n = (160 * 1024) / Gm::LDS;
+    if (n > 4) n = 4;  // 4 x 512 threads: 32 waves per CU
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, hconv_kernel<C, COUT, TR, TC, BNB>, 512, 0) == hipSuccess &&
+        occ >= 1 && occ < n)
+      n = occ;
+    return n;
+  }();
   const int g = 256 * per_cu < ntiles ? 256 * per_cu : ntiles;
   static const char* nm = nullptr;
   static char buf[64];
@@ -535,14 +572,17 @@ static void hconv_go(const PgArgs& a, hipStream_t st) {
     nm = buf;
   }
   set_last_kernel(nm);
-  hipLaunchKernelGGL((hconv_kernel<C, COUT, TR, TC, BNB>), dim3(g), dim3(320), 0, st, a, ntiles);
+  hipLaunchKernelGGL((hconv_kernel<C, COUT, TR, TC, BNB>), dim3(g), dim3(512), 0, st, a, ntiles);
 }
 
 template <int C, int COUT, bool BNB>
 static void hconv_tiles(const PgArgs& a, hipStream_t st) {
-  // 16 x 16 tiles when the image splits evenly (stem, 112 x 112), else 8 x 16
-  if (a.Ho % 16 == 0 && a.Wo % 16 == 0) hconv_go<C, COUT, 16, 16, BNB>(a, st);
-  else hconv_go<C, COUT, 8, 16, BNB>(a, st);
+  // 16 x 16 tiles when the image splits evenly (stem, 112 x 112) and three such halos fit the LDS
+  // beside the filters (not 64 -> 64), else 8 x 16
+  if constexpr (HcGeom<C, COUT, 16, 16, BNB>::FITS) {
+    if (a.Ho % 16 == 0 && a.Wo % 16 == 0) return hconv_go<C, COUT, 16, 16, BNB>(a, st);
+  }
+  hconv_go<C, COUT, 8, 16, BNB>(a, st);
 }
 
 template <bool BNB>
