@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 import _hip
 import _kernels
+from _convref import bnb_reference as _bnb_reference, pack_bits as _pack_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -91,27 +92,6 @@ BNB_CASES = [
     (4, 2, 16, 16, 512, 128, 1, 0, 0, 2, 1),   # RES, K 128 (layer-2 conv1 family), two targets
     (6, 3, 8, 8, 256, 128, 1, 0, 0, 1, 2),     # RES, K 128, avg-unpool residual
 ]
-
-
-def _bnb_reference(d, kind, ys, means, istds, msc, msh, mask):
-    """g = d*mask, sum g, sum g*xhat_t (f64) for one segment; tensors [n, C];
-    kind 1 masks with the ReLU's BN applied as (y - mean) * scale + beta"""
-    if kind == 1:
-        keep = ((ys[0] - means[0]) * msc + msh) > 0
-    else:
-        keep = mask > 0
-    g = torch.where(keep, d, torch.zeros_like(d))
-    sums = []
-    for y, m, s in zip(ys, means, istds):
-        xhat = (y - m) * s
-        sums.append((g.sum(0), (g * xhat).sum(0)))
-    return g, sums
-
-
-def _pack_bits(mask_nhwc):
-    """[..., C] -> uint8 [..., C/8]: bit e of byte c = mask[..., 8c+e] > 0"""
-    m = (mask_nhwc > 0).to(torch.uint8).reshape(*mask_nhwc.shape[:-1], -1, 8)
-    return (m << torch.arange(8, dtype=torch.uint8, device=m.device)).sum(-1).to(torch.uint8)
 
 
 @pytest.mark.parametrize("bits", [False, True])
