@@ -239,11 +239,21 @@ __global__ void __launch_bounds__(256) conv_gemm_kernel(ConvArgs a) {
     for (int i = 0; i < BRows; ++i) *reinterpret_cast<uint4*>(Bs + (lc * (BN + 1) + lr + 32 * i) * 16) = rb[i];
   };
 
+  // f32 accumulates each K-step (a chain of 8 MFMAs) from zero and adds the step's sum to a
+  // running total: one chain over all of K carries the rounding of K/4 sequential additions at the
+  // full magnitude of y (rms 9 * 2^-24 at K = 1600), which, squared and summed over a short BN
+  // segment, is more than the statistics' 8 * 2^-24 * sum y^2 allows; per K-step it is K/32
+  // additions (rms 2 * 2^-24).  bf16 keeps the single chain.
+  constexpr bool STEP_SUMS = EPC == 4;
   f32x4 acc[MT][NT];
+  f32x4 total[STEP_SUMS ? MT : 1][STEP_SUMS ? NT : 1];
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NT; ++j) {
+      acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (STEP_SUMS) total[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 
   const int nk = (a.K + BK - 1) / BK;
   load_tiles(0);
@@ -270,8 +280,23 @@ __global__ void __launch_bounds__(256) conv_gemm_kernel(ConvArgs a) {
 #pragma unroll
         for (int j = 0; j < NT; ++j) MM<T>::mma(acc[i][j], af[i], bfr[j]);
     }
+    if constexpr (STEP_SUMS) {
+#pragma unroll
+      for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+          total[i][j] += acc[i][j];
+          acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
     if (kt + 1 < nk) store_tiles(cur ^ 1);
     __syncthreads();
+  }
+  if constexpr (STEP_SUMS) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+      for (int j = 0; j < NT; ++j) acc[i][j] = total[i][j];
   }
 
   // ---- epilogue 1: batch-norm statistics straight from the accumulators
