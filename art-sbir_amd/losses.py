@@ -12,6 +12,8 @@
                                the reference trains on the negative the dataset drew)
   CrossBatchMemory             a ring of past gallery-side embeddings on the device that the
                                mining above can search as well (an addition)
+  info_nce / InfoNCELoss       the softmax contrastive loss over all 2B gallery-side rows of
+                               the step and that ring (an addition)
 All run on the GPU kernels with explicit backward kernels.
 """
 from __future__ import annotations
@@ -438,3 +440,111 @@ class MinedNegatives(nn.Module):
         """anchors whose selection is a slot of the memory / anchors seen with the memory
         since the last call (0.0 when none was seen); resets both"""
         return self._fraction(2)
+
+
+# ------------------------------------------------------------ InfoNCE over the batch and the memory
+def _info_nce_raw(a, p, n, temperature, cand_ids, memory, eps, with_grad):
+    """one artsbir_info_nce call: (loss [], rows [B], q [B], (da, dp, dn) or None)"""
+    _cuda(a, p, n)
+    a, p, n = (t.detach().contiguous().float() for t in (a, p, n))
+    if not (a.dim() == 2 and a.shape == p.shape == n.shape):
+        raise ValueError(f"a, p, n must share one [B, D] shape: {tuple(a.shape)} {tuple(p.shape)} {tuple(n.shape)}")
+    temperature = float(temperature)
+    if not temperature > 0:
+        raise ValueError(f"temperature must be > 0, not {temperature}")
+    B, D = a.shape
+    if cand_ids is not None:
+        _cuda(cand_ids)
+        cand_ids = cand_ids.detach().contiguous().to(torch.int64)
+        if cand_ids.shape != (2 * B,):
+            raise ValueError(f"cand_ids must have shape [{2 * B}], not {tuple(cand_ids.shape)}")
+    mem = mem_ids = mem_state = None
+    M = 0
+    if memory is not None:
+        memory._ready(a)
+        mem, mem_ids, mem_state, M = memory.mem, memory.mem_ids, memory.mem_state, memory.size
+    nbytes = _hip.lib().artsbir_info_nce_workspace(B, D, M, int(with_grad))
+    if nbytes < 0:
+        raise _hip.HipError(_hip.lib().artsbir_last_error().decode(errors="replace"))
+    ws = torch.empty(max(int(nbytes), 4), dtype=torch.uint8, device=a.device)
+    loss = torch.empty((), dtype=torch.float32, device=a.device)
+    rows, q = (torch.empty(B, dtype=torch.float32, device=a.device) for _ in range(2))
+    grads = tuple(torch.empty_like(a) for _ in range(3)) if with_grad else (None, None, None)
+    call("artsbir_info_nce", ptr(a), ptr(p), ptr(n), B, D, 1.0 / temperature, float(eps), ptr(cand_ids), ptr(mem),
+         ptr(mem_ids), ptr(mem_state), M, ptr(loss), ptr(rows), ptr(q), ptr(grads[0]), ptr(grads[1]), ptr(grads[2]),
+         ptr(ws), int(nbytes), _s())
+    return loss, rows, q, (grads if with_grad else None)
+
+
+class _InfoNCEFn(torch.autograd.Function):
+    """The forward asks artsbir_info_nce for the gradients too when any input needs one:
+    they are taken from the ring as the forward saw it (an enqueue right after the forward
+    changes the ring), and the backward only scales them."""
+
+    @staticmethod
+    def forward(ctx, a, p, n, temperature, cand_ids, memory, eps):
+        with_grad = any(ctx.needs_input_grad[:3])
+        loss, rows, q, grads = _info_nce_raw(a, p, n, temperature, cand_ids, memory, eps, with_grad)
+        if with_grad:
+            ctx.save_for_backward(*grads)
+        ctx.mark_non_differentiable(q)
+        return loss, q
+
+    @staticmethod
+    def backward(ctx, gout, _gq):
+        da, dp, dn = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        return (gout * da if need[0] else None, gout * dp if need[1] else None, gout * dn if need[2] else None,
+                None, None, None, None)
+
+
+def info_nce(a, p, n, temperature=0.07, cand_ids=None, memory=None, eps=1e-8):
+    """InfoNCE (softmax contrastive) loss of every anchor a[i] against its positive p[i] and
+    every other gallery-side row of the step, C = [p; n], and of a CrossBatchMemory's filled
+    slots: mean over i of -log softmax_i(positive) of the logits cos(a[i], c) / temperature.
+    Candidate c != i is a negative unless cand_ids (int64 [2B], the photo of every row of C)
+    is given and the candidate's photo (cand_ids[c], memory.mem_ids[j]) is cand_ids[i].
+    Exact f32 on the f32-input MFMA; the logit matrix never exists in memory; two runs give
+    the same bytes.  Gradients flow to a, p and n; ring rows are constants."""
+    return _InfoNCEFn.apply(a, p, n, temperature, cand_ids, memory, eps)[0]
+
+
+class InfoNCELoss(nn.Module):
+    """forward(a, p, n, cand_ids=None) = info_nce(a, p, n, temperature, cand_ids, memory).
+    memory (a CrossBatchMemory, default None): with gradients enabled the ring's filled slots
+    are negatives too, and cat(p, n).detach() with cand_ids is enqueued after the loss has
+    read the ring, so a step never meets its own rows; under torch.no_grad() the ring is
+    neither read nor written.  A device counter (no host synchronisation) follows the
+    probability of the positive, 1 - q, over the anchors seen with gradients enabled;
+    positive_probability() reads and resets it."""
+
+    margin = None  # there is no margin: the triplet losses' attribute, for the training record
+
+    def __init__(self, temperature: float = 0.07, memory=None):
+        super().__init__()
+        if not float(temperature) > 0:
+            raise ValueError(f"temperature must be > 0, not {temperature}")
+        self.temperature, self.memory = float(temperature), memory
+        self._sums = None  # f64 [2] on the device: anchors seen, sum of 1 - q
+
+    def forward(self, anchor, positive, negative, cand_ids=None):
+        grad = torch.is_grad_enabled()
+        memory = self.memory if grad else None
+        loss, q = _InfoNCEFn.apply(anchor, positive, negative, self.temperature, cand_ids, memory, 1e-8)
+        if grad:
+            if self._sums is None or self._sums.device != q.device:
+                self._sums = torch.zeros(2, dtype=torch.float64, device=q.device)
+            self._sums[0] += q.shape[0]
+            self._sums[1] += (1.0 - q.double()).sum()
+            if memory is not None:
+                memory.enqueue(torch.cat((positive, negative)).detach(), cand_ids)
+        return loss
+
+    def positive_probability(self) -> float:
+        """mean probability of the positive over the anchors seen with gradients enabled
+        since the last call (0.0 when none was seen); resets"""
+        if self._sums is None:
+            return 0.0
+        seen, total = self._sums.tolist()
+        self._sums.zero_()
+        return total / seen if seen else 0.0

@@ -22,7 +22,10 @@ Differences, all opt-in or documented:
     (losses.MinedNegatives); every process mines in its own shard;
   * ``--memory_size M`` adds a ring of the last M gallery-side embeddings to the
     candidates of ``--negatives`` (losses.CrossBatchMemory); under
-    torch.distributed.run the ring holds every rank's rows, so negatives cross ranks.
+    torch.distributed.run the ring holds every rank's rows, so negatives cross ranks;
+  * ``--negatives all --loss_type cosine`` trains with the InfoNCE (softmax contrastive)
+    loss over all 2 x batch gallery-side embeddings of the step and the ring
+    (losses.InfoNCELoss), at ``--temperature``.
 """
 from __future__ import annotations
 
@@ -46,7 +49,7 @@ device = "cuda" if torch.cuda.is_available() else "cpu"
 
 
 def get_loss(loss_fn, model, elements):
-    if isinstance(loss_fn, losses.MinedNegatives):
+    if isinstance(loss_fn, (losses.MinedNegatives, losses.InfoNCELoss)):
         # the items end with the positive's and the negative's photo number
         # (get_datasets(ids=True)): the identities of the 2B mining candidates
         cand_ids = torch.cat((elements[-2], elements[-1]))
@@ -92,6 +95,8 @@ def _triplet_train(model, epochs, train_dataloader, test_dataloader, loss_fn, op
     mined_fraction = []  # per epoch: the share of training anchors whose negative was replaced
     with_memory = mining and loss_fn.memory is not None
     memory_fraction = []  # per epoch: the share whose negative came from the cross-batch memory
+    contrastive = isinstance(loss_fn, losses.InfoNCELoss)
+    positive_probability = []  # per epoch: the mean softmax probability of the positive (InfoNCE)
     iteration_loss_frequency = 10000 // train_dataloader.batch_size if epochs <= 6 else 0
     itest_size = max(1000 // test_dataloader.batch_size, 1)
     for epoch in range(epochs):
@@ -119,6 +124,8 @@ def _triplet_train(model, epochs, train_dataloader, test_dataloader, loss_fn, op
             mined_fraction.append(loss_fn.mined_fraction())
         if with_memory:
             memory_fraction.append(loss_fn.memory_fraction())
+        if contrastive:
+            positive_probability.append(loss_fn.positive_probability())
         test_loss = _evaluate(model, loss_fn, test_dataloader, elements if stale_eval else None, None)
         train_losses.append(train_loss.item() / max(len(train_dataloader), 1))
         test_losses.append(test_loss / max(len(test_dataloader), 1))
@@ -131,6 +138,8 @@ def _triplet_train(model, epochs, train_dataloader, test_dataloader, loss_fn, op
         out["mined_fraction"] = mined_fraction
     if with_memory:
         out["memory_fraction"] = memory_fraction
+    if contrastive:
+        out["positive_probability"] = positive_probability
     return out
 
 
@@ -158,16 +167,21 @@ def _evaluate(model, loss_fn, loader, stale, limit):
     return total
 
 
-def make_loss(loss_type, with_classification, dataset_name, margin, negatives='given', memory_size=0):
+def make_loss(loss_type, with_classification, dataset_name, margin, negatives='given', memory_size=0,
+              temperature=None):
     """the reference's loss for the configuration; negatives 'hardest' / 'semihard' wraps
-    it in losses.MinedNegatives with the metric of loss_type, memory_size > 0 gives that a
+    it in losses.MinedNegatives with the metric of loss_type, 'all' gives losses.InfoNCELoss
+    at `temperature` (default 0.07) instead; memory_size > 0 gives either a
     losses.CrossBatchMemory of memory_size rows (of the embeddings' width, allocated at the
     first step)"""
     _check_memory_size(memory_size, negatives)
+    _check_contrastive(negatives, temperature, loss_type, with_classification)
+    memory = losses.CrossBatchMemory(memory_size, None) if memory_size else None
+    if negatives == 'all':
+        return losses.InfoNCELoss(DEFAULT_TEMPERATURE if temperature is None else temperature, memory=memory)
     loss_fn = _make_loss(loss_type, with_classification, dataset_name, margin)
     if negatives == 'given':
         return loss_fn
-    memory = losses.CrossBatchMemory(memory_size, None) if memory_size else None
     return losses.MinedNegatives(loss_fn, mode=negatives, metric=loss_type, memory=memory)
 
 
@@ -177,6 +191,26 @@ def _check_memory_size(memory_size, negatives):
     if memory_size and negatives == 'given':
         raise SystemExit("--memory_size needs --negatives hardest or semihard: the memory only adds candidates "
                          "to the mining")
+
+
+DEFAULT_TEMPERATURE = 0.07
+
+
+def _check_contrastive(negatives, temperature, loss_type=None, with_classification=False):
+    """--negatives all / --temperature; loss_type None: not known yet (parse time checks it
+    from the arguments)"""
+    if negatives != 'all':
+        if temperature is not None:
+            raise SystemExit("--temperature needs --negatives all: only the InfoNCE loss has a temperature")
+        return
+    if temperature is not None and not temperature > 0:
+        raise SystemExit(f"--temperature {temperature} must be > 0")
+    if loss_type is not None and loss_type != 'cosine':
+        raise SystemExit("--negatives all needs --loss_type cosine: the InfoNCE loss trains the cosine similarity, "
+                         "and inference must rank by the similarity that was trained")
+    if with_classification:
+        raise SystemExit("--negatives all needs a model without classification heads: the InfoNCE loss is not "
+                         "combined with the classification composites")
 
 
 def _make_loss(loss_type, with_classification, dataset_name, margin):
@@ -241,17 +275,23 @@ def parse_args(argv=None):
     p.add_argument('--fresh_eval', dest='stale_eval', action='store_false',
                    help="test loss over the test batches instead of the stale train batch")
     p.add_argument('--no_save', action='store_true')
-    p.add_argument('--negatives', default='given', choices=['given', 'hardest', 'semihard'],
+    p.add_argument('--negatives', default='given', choices=['given', 'hardest', 'semihard', 'all'],
                    help="the negative of every triplet: the one the dataset drew (the reference), or mined among "
                         "the 2 x batch gallery-side embeddings of the step (losses.MinedNegatives; per process "
                         "under torch.distributed.run: the step's candidates are not exchanged between ranks, "
-                        "--memory_size adds past rows of every rank)")
+                        "--memory_size adds past rows of every rank); all: every one of them, by the InfoNCE "
+                        "loss (losses.InfoNCELoss; needs --loss_type cosine and no classification heads)")
+    p.add_argument('--temperature', type=float, default=None,
+                   help="temperature of the InfoNCE loss (--negatives all; default 0.07)")
     p.add_argument('--memory_size', type=int, default=0,
                    help="cross-batch memory: also mine among the last M gallery-side embeddings of earlier steps, "
                         "of every rank under torch.distributed.run (losses.CrossBatchMemory; 0 = off; needs "
                         "--negatives hardest or semihard)")
     args = p.parse_args(argv)
     _check_memory_size(args.memory_size, args.negatives)
+    _check_contrastive(args.negatives, args.temperature, args.loss_type, 'with_classification' in args.model_type)
+    if args.negatives == 'all' and args.temperature is None:
+        args.temperature = DEFAULT_TEMPERATURE
     return args
 
 
@@ -292,7 +332,7 @@ def main(argv=None):
     optimizer = optim.Adam(model.parameters(), lr=args.learning_rate, weight_decay=args.weight_decay)
     with_classification = 'with_classification' in type(model).__name__ and 'V2' in train_dataset.state_dict['dataset']
     loss_fn = make_loss(args.loss_type, with_classification, train_dataset.state_dict['dataset'], utils.MARGIN,
-                        args.negatives, args.memory_size)
+                        args.negatives, args.memory_size, args.temperature)
     param_dict = {"model": args.model, "trained_layers": model.trained_layers, "dataset": args.dataset,
                   "epochs": args.epochs, "batch_size": args.batch_size, "learning_rate": args.learning_rate,
                   "weight_decay": args.weight_decay, "optimizer": type(optimizer).__name__,
@@ -300,6 +340,8 @@ def main(argv=None):
                   "dtype": args.dtype}
     if args.negatives != 'given':
         param_dict["negatives"] = args.negatives
+    if args.negatives == 'all':
+        param_dict["temperature"] = args.temperature
     if args.memory_size:
         param_dict["memory_size"] = args.memory_size
     data_dict = train_dataset.state_dict

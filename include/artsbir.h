@@ -494,6 +494,26 @@ int artsbir_xbm_enqueue(const float* rows, const long long* ids, int R, int D, f
  * selection >= 2B is a constant and adds to no row. */
 int artsbir_rows_gather3(const float* p, const float* n, const float* mem, const long long* sel, int B, int D, int M,
                          float* out, void* stream);
+/* InfoNCE (softmax contrastive) loss over the batch and the cross-batch memory
+ * (csrc/contrast.hip; an addition, as the mining above).  Candidates are those of
+ * artsbir_mine_pool: c < B is p[c], B <= c < 2B is n[c - B], c = 2B + j is slot j for
+ * j < min(count, M), count read on the device.  c = i is anchor i's positive; every other
+ * candidate is a negative unless cand_ids is given and the candidate's id (cand_ids[c],
+ * mem_ids[j]) equals cand_ids[i].  With x^ = x / max(|x|, eps), z(i, c) = scale * a^_i . c^_c:
+ *   L_i = log sum over the negatives of exp z(i, c) (-inf with none), u_i = L_i - z(i, i),
+ *   rows[i] = softplus(u_i), q[i] = sigmoid(u_i) (both 0 with no negative), loss = mean rows.
+ * With da, dp, dn (all three or none) the same call also writes the gradients of the loss
+ * for d loss = 1, from the ring as the forward saw it; ring rows are constants.  Exact
+ * f32 (f32-input MFMA), no atomics: two runs give the same bytes.  The logits never
+ * exist in memory; ws (artsbir_info_nce_workspace bytes, 8-byte aligned) holds inverse
+ * norms (8 bytes per slot of M) and per-share partials.  M = 0, mem NULL and count = 0
+ * give the same bytes.  1 <= B <= 2^20, 1 <= D <= 1024, 0 <= M <= 2^24, scale finite
+ * and > 0; mem needs mem_state, and mem_ids when cand_ids is given.  A NaN propagates. */
+long long artsbir_info_nce_workspace(int B, int D, int M, int with_grad);
+int artsbir_info_nce(const float* a, const float* p, const float* n, int B, int D, float scale, float eps,
+                     const long long* cand_ids, const float* mem, const long long* mem_ids,
+                     const long long* mem_state, int M, float* loss, float* rows, float* q, float* da, float* dp,
+                     float* dn, void* ws, long long ws_bytes, void* stream);
 /* Adam over a device table of {param, grad, exp_avg, exp_avg_sq, numel} records
  * (host helpers size and fill the per-block table). */
 long long artsbir_adam_table_blocks(const long long* numels, int ntensors, long long chunk);

@@ -4,9 +4,11 @@ batch and tuning table) through train.triplet_train with the given negatives and
 with --negatives hardest / semihard, alternating on the same device: ms per step
 from device events recorded as the loop fetches each batch.  With --memory_size M the
 forms are --negatives hardest alone and with a cross-batch memory of M rows, filled
-with random rows ahead of the first step so that every timed step scans all M.
+with random rows ahead of the first step so that every timed step scans all M.  With
+--negatives all the forms are the given negatives and the InfoNCE loss over the batch
+(losses.InfoNCELoss, cosine) and, with --memory_size M, over the batch and a full ring too.
 
-    python tools/mining_step.py [--steps 10] [--warmup 3] [--memory_size M] [--out FILE]"""
+    python tools/mining_step.py [--steps 10] [--warmup 3] [--negatives all] [--memory_size M] [--out FILE]"""
 import argparse
 import os
 import statistics
@@ -49,7 +51,8 @@ def run(negatives, batch, args, dev, memory_size=0):
                                   width=bench.WIDTH).to(dev)
     model.compute_dtype = torch.bfloat16
     opt = optim.Adam(model.parameters(), lr=1e-5, weight_decay=0.002)
-    loss_fn = train.make_loss("euclidean", False, "Synthetic", 0.2, negatives, memory_size)
+    loss_fn = train.make_loss("cosine" if negatives == "all" else "euclidean", False, "Synthetic", 0.2, negatives,
+                              memory_size)
     B = batch[0].shape[0]
     if memory_size:  # a full ring from the first step on (768 rows a step would take M / 768 steps)
         loss_fn.memory.enqueue(torch.randn(memory_size, bench.OUT_DIM, device=dev))
@@ -60,7 +63,7 @@ def run(negatives, batch, args, dev, memory_size=0):
     torch.cuda.synchronize()
     ev = loader.events[args.warmup:]
     ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(len(ev) - 1)]
-    return statistics.median(ms), min(ms), out
+    return statistics.median(ms), min(ms), out, ms
 
 
 def main():
@@ -70,6 +73,8 @@ def main():
     ap.add_argument("--batch", type=int, default=384)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--memory_size", type=int, default=0)
+    ap.add_argument("--negatives", default=None, choices=["all"],
+                    help="all: time the InfoNCE loss against the given negatives")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -88,15 +93,23 @@ def main():
     forms = [("given", 0), ("hardest", 0), ("semihard", 0)]
     if args.memory_size:
         forms = [("hardest", 0), ("hardest", args.memory_size)]
+    if args.negatives == "all":
+        forms = [("given", 0), ("all", 0)] + ([("all", args.memory_size)] if args.memory_size else [])
     for r in range(args.rounds):
         for negatives, memory_size in forms:
-            med, best, out = run(negatives, batch, args, dev, memory_size)
+            med, best, out, ms = run(negatives, batch, args, dev, memory_size)
             extra = f" mined_fraction={out['mined_fraction'][0]:.3f}" if "mined_fraction" in out else ""
             if "memory_fraction" in out:
                 extra += f" memory_size={memory_size} memory_fraction={out['memory_fraction'][0]:.3f}"
+            if "positive_probability" in out:
+                extra += f" memory_size={memory_size} positive_probability={out['positive_probability'][0]:.4f}"
             lines.append(f"C2 step B={B} round={r} negatives={negatives:<8s} median={med:.2f} ms min={best:.2f} ms "
                          f"over {args.steps} steps train_loss={out['train_losses'][0]:.5f}{extra}")
             print(lines[-1], flush=True)
+            if args.negatives == "all":  # every step of the run
+                lines.append(f"raw round={r} negatives={negatives} memory_size={memory_size} ms=" +
+                             " ".join(f"{v:.2f}" for v in ms))
+                print(lines[-1], flush=True)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
