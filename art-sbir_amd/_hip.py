@@ -176,6 +176,9 @@ SIGNATURES = {
     "artsbir_info_nce_workspace": [_c_int, _c_int, _c_int, _c_int],
     "artsbir_info_nce": [_vp, _vp, _vp, _c_int, _c_int, _c_float, _c_float, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _vp,
                          _vp, _vp, _vp, _vp, _c_ll, _vp],
+    "artsbir_info_nce_pool_workspace": [_c_int, _c_int, _c_int, _c_int, _c_int],
+    "artsbir_info_nce_pool": [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _vp, _vp, _vp, _vp, _c_int,
+                              _vp, _vp, _vp, _vp, _vp, _vp, _c_ll, _vp],
     "artsbir_adam_table_blocks": [_vp, _c_int, _c_ll],
     "artsbir_adam_fill_table": [_vp, _c_int, _c_ll, _vp],
     "artsbir_adam_step": [_vp, _vp, _c_ll, _c_ll, _c_float, _c_float, _c_float, _c_float, _c_float, _c_ll, _vp],
@@ -212,7 +215,8 @@ SIGNATURES = {
 }
 _RESTYPES = {"artsbir_last_error": ctypes.c_char_p, "artsbir_last_kernel": ctypes.c_char_p, "artsbir_adam_table_blocks": _c_ll,
              "artsbir_knn_candidates_per_query": _c_int, "artsbir_pairwise_l2_topk_workspace": _c_ll,
-             "artsbir_clip_preprocess_workspace": _c_ll, "artsbir_info_nce_workspace": _c_ll}
+             "artsbir_clip_preprocess_workspace": _c_ll, "artsbir_info_nce_workspace": _c_ll,
+             "artsbir_info_nce_pool_workspace": _c_ll}
 
 _lib = None
 

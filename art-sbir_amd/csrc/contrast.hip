@@ -4,7 +4,10 @@
 // Candidates use the index space of mining.hip / xbm.hip: c < B is p[c], B <= c < 2B is
 // n[c - B], c = 2B + j is slot j of the ring for j < min(count, M) (count read on the
 // device).  c = i is anchor i's positive; every other candidate is a negative unless ids
-// are given and the candidate's id equals cand_ids[i].  With x^ = x / max(|x|, eps) and
+// are given and the candidate's id equals cand_ids[i].  The pool form (artsbir_info_nce_pool)
+// runs the same kernels over one block cand [Nc][D] of gradient-carrying candidates in place
+// of [p; n] (the ring starts at c = Nc) with anchor i's positive at c = pos0 + i: the rows of
+// every rank, of which the local anchors' own are a slice.  With x^ = x / max(|x|, eps) and
 // z(i, c) = scale * a^_i . c^_c, in the stable form:
 //   L_i = log sum_{negatives} exp z(i, c)   (-inf with no negative)
 //   u_i = L_i - z(i, i),  row_i = softplus(u_i),  q_i = sigmoid(u_i),  loss = mean row_i
@@ -28,11 +31,11 @@
 //
 // Launches (no host synchronisation, no floating-point atomics: two runs give the
 // same bytes):
-//   nce_prep_kernel      inverse clamped norms of a, [p; n] and the filled slots
+//   nce_prep_kernel      inverse clamped norms of a, the batch candidates and the filled slots
 //   nce_fwd_kernel       grid anchor tiles x candidate shares (nce_block): an online log-sum-exp per
 //                        lane over the share's tiles, met across the lanes and the four
 //                        waves in a fixed order -> one (max, sum) per (share, anchor);
-//                        the tile that holds c = i stores z(i, i)
+//                        the tile that holds anchor i's positive stores z(i, i)
 //   nce_lse_kernel       the shares' pairs in share order -> L, rows, q
 //   nce_mean_kernel      loss = mean rows, one workgroup, fixed order
 //   nce_da_kernel<ND>    the same grid: z recomputed, W diag(invc) through
@@ -40,11 +43,11 @@
 //                        tile: one transpose), W . C accumulated in registers over the
 //                        share (wave w owns 16 ND columns of the 32 anchors) -> a partial
 //                        da^ tile per share
-//   nce_dc_kernel        grid (candidate tiles of [p; n], 256-column blocks): walks all
+//   nce_dc_kernel        grid (tiles of the batch candidates, 256-column blocks): walks all
 //                        anchors; the logit accumulators are the A operand of W^T . A as
 //                        they stand (the product sums over their register index), so a
 //                        dc^ tile has one owner and no partials
-//   nce_finish_kernel    a wave per row of da, dp, dn: the da^ partials in share order,
+//   nce_finish_kernel    a wave per row of da and of dp, dn | dcand: the da^ partials in share order,
 //                        scale / B and the backward of the normalisation
 // An empty share and an all-masked row are (-inf, 0); the combine never forms inf - inf.
 // A row past the filled part of the ring is never read: row indices are clamped to the
@@ -65,22 +68,50 @@ namespace artsbir {
 #define NCE_MAX_D 1024
 #define NCE_DC_COLS 256       // columns of a dc^ tile: 16 accumulators of 16
 
-struct NcePool {
-  const float* p;
-  const float* n;
-  const float* mem;
-  int B, D, ctot;  // ctot = 2B + filled slots
+// The candidates of a call.  c < split is row c of c0, split <= c < nb row c - split of c1,
+// c = nb + j slot j of the ring; anchor i's positive is c = pos0 + i.
+//   artsbir_info_nce        c0 = p, c1 = n, split = B, nb = 2B, pos0 = 0
+//   artsbir_info_nce_pool   c0 = cand (c1 unused), split = nb = Nc, pos0 as given
+struct NceGeo {
+  int B, D, split, nb, pos0;
 };
+
+struct NcePool {
+  const float* c0;
+  const float* c1;
+  const float* mem;
+  int B, D, split, nb, pos0;
+  int ctot;  // nb + filled slots
+};
+
+// row c of the blocks (mine_dev.h's cand_row / pool_row with the two bounds of their own)
+__device__ __forceinline__ const float* nce_batch_row(const float* __restrict__ c0, const float* __restrict__ c1, int split,
+                                                      int D, int c) {
+  return c < split ? c0 + (long long)c * D : c1 + (long long)(c - split) * D;
+}
+
+__device__ __forceinline__ const float* nce_pool_row(const float* __restrict__ c0, const float* __restrict__ c1,
+                                                     const float* __restrict__ mem, int split, int nb, int D, int c) {
+  return c < nb ? nce_batch_row(c0, c1, split, D, c) : mem + (long long)(c - nb) * D;
+}
 
 // the row of candidate c; past the last candidate the last one again (masked by the caller)
 __device__ __forceinline__ const float* nce_row(const NcePool& pl, int c) {
-  return pool_row(pl.p, pl.n, pl.mem, pl.B, pl.D, min(c, pl.ctot - 1));
+  c = min(c, pl.ctot - 1);
+  return nce_pool_row(pl.c0, pl.c1, pl.mem, pl.split, pl.nb, pl.D, c);
 }
 
 __device__ __forceinline__ int nce_filled(const float* mem, const long long* __restrict__ state, int M) {
   if (!mem || M <= 0) return 0;
   const long long c = state[1];
   return c < 0 ? 0 : (c > M ? M : (int)c);
+}
+
+// the pool as a kernel sees it: the filled part of the ring is read here (state NULL: no ring)
+__device__ __forceinline__ NcePool nce_open(const float* __restrict__ r0, const float* __restrict__ r1,
+                                            const float* __restrict__ mem, const NceGeo& g,
+                                            const long long* __restrict__ state, int M) {
+  return NcePool{r0, r1, mem, g.B, g.D, g.split, g.nb, g.pos0, g.nb + (state ? nce_filled(mem, state, M) : 0)};
 }
 
 // four values of a row from column k; columns past D read as 0
@@ -170,6 +201,7 @@ __device__ __forceinline__ void nce_logits_tile(const float* __restrict__ a, int
 // what a lane knows of its candidate column of a tile
 struct NceCol {
   int c;        // pool index
+  int rel;      // c - pos0: the anchor whose positive this candidate is, where that is one of the tile's
   bool valid;   // c < ctot
   double inv;   // inverse clamped norm
   long long id;
@@ -180,10 +212,11 @@ __device__ __forceinline__ NceCol nce_col(const NcePool& pl, int c, const double
                                           const long long* __restrict__ mem_ids) {
   NceCol col;
   col.c = c;
+  col.rel = c - pl.pos0;
   col.valid = c < pl.ctot;
   const int cc = min(c, pl.ctot - 1);
-  col.inv = cc < 2 * pl.B ? invc[cc] : invm[cc - 2 * pl.B];
-  col.id = !cand_ids ? 0 : (cc < 2 * pl.B ? cand_ids[cc] : mem_ids[cc - 2 * pl.B]);
+  col.inv = cc < pl.nb ? invc[cc] : invm[cc - pl.nb];
+  col.id = !cand_ids ? 0 : (cc < pl.nb ? cand_ids[cc] : mem_ids[cc - pl.nb]);
   return col;
 }
 
@@ -220,21 +253,24 @@ __device__ __forceinline__ bool nce_block(int nta, int ns, int& tile, int& share
   return true;
 }
 
-// one wave per row: inverse clamped norms.  rows [0, B) a, [B, 3B) [p; n], then the filled slots
+// one wave per row: inverse clamped norms.  rows [0, B) a, [B, B + nb) the batch candidates,
+// then the filled slots
 __global__ void __launch_bounds__(256)
-    nce_prep_kernel(const float* __restrict__ a, const float* __restrict__ p, const float* __restrict__ n, int B, int D,
-                    float eps, const float* __restrict__ mem, const long long* __restrict__ mem_state, int M,
+    nce_prep_kernel(const float* __restrict__ a, const float* __restrict__ r0, const float* __restrict__ r1, const float* __restrict__ mem, NceGeo geo, float eps, const long long* __restrict__ mem_state, int M,
                     double* __restrict__ inva, double* __restrict__ invc, double* __restrict__ invm) {
   const int lane = threadIdx.x & 63;
-  const int filled = nce_filled(mem, mem_state, M);
-  const long long total = 3LL * B + filled;
+  const NcePool pl = nce_open(r0, r1, mem, geo, mem_state, M);
+  const int B = pl.B, D = pl.D;
+  const long long total = (long long)B + pl.ctot;
   for (long long r = blockIdx.x * 4LL + (threadIdx.x >> 6); r < total; r += 4LL * gridDim.x) {
     const float* row;
     double* out;
     if (r < B) { row = a + r * D; out = inva + r; }
-    else if (r < 2LL * B) { row = p + (r - B) * D; out = invc + (r - B); }
-    else if (r < 3LL * B) { row = n + (r - 2LL * B) * D; out = invc + (r - B); }
-    else { row = mem + (r - 3LL * B) * D; out = invm + (r - 3LL * B); }
+    else {
+      const int c = (int)(r - B);
+      row = nce_row(pl, c);
+      out = c < pl.nb ? invc + c : invm + (c - pl.nb);
+    }
     double ss = 0.0;
     for (int d = lane; d < D; d += 64) ss = fma((double)row[d], (double)row[d], ss);
 #pragma unroll
@@ -244,8 +280,7 @@ __global__ void __launch_bounds__(256)
 }
 
 __global__ void __launch_bounds__(256)
-    nce_fwd_kernel(const float* __restrict__ a, const float* __restrict__ p, const float* __restrict__ n, int B, int D,
-                   float scale, const long long* __restrict__ cand_ids, const float* __restrict__ mem,
+    nce_fwd_kernel(const float* __restrict__ a, const float* __restrict__ r0, const float* __restrict__ r1, const float* __restrict__ mem, NceGeo geo, float scale, const long long* __restrict__ cand_ids,
                    const long long* __restrict__ mem_ids, const long long* __restrict__ mem_state, int M, int vec,
                    const double* __restrict__ inva, const double* __restrict__ invc, const double* __restrict__ invm,
                    double* __restrict__ zpos, double* __restrict__ part, int nta, int ns) {
@@ -255,7 +290,8 @@ __global__ void __launch_bounds__(256)
   __shared__ __attribute__((aligned(16))) float Cs[NCE_TC * NCE_LD];
   __shared__ double red[4][NCE_TA][2];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, g = lane >> 4;
-  NcePool pl{p, n, mem, B, D, 2 * B + nce_filled(mem, mem_state, M)};
+  const NcePool pl = nce_open(r0, r1, mem, geo, mem_state, M);
+  const int B = pl.B;
   const int i0 = tile * NCE_TA;
   double ia[2][4], m[2][4];
   float s[2][4];
@@ -266,7 +302,7 @@ __global__ void __launch_bounds__(256)
     for (int r = 0; r < 4; ++r) {
       const int i = min(i0 + 16 * h + 4 * g + r, B - 1);
       ia[h][r] = inva[i];
-      aid[h][r] = cand_ids ? cand_ids[i] : 0;
+      aid[h][r] = cand_ids ? cand_ids[pl.pos0 + i] : 0;
       m[h][r] = -INFINITY;
       s[h][r] = 0.f;
     }
@@ -283,7 +319,7 @@ __global__ void __launch_bounds__(256)
           const int i = i0 + 16 * h + 4 * g + r;
           if (i < B) {
             const double z = nce_z(acc[h][r], ia[h][r], col.inv, scale);
-            if (col.c == i) zpos[i] = z;
+            if (col.rel == i) zpos[i] = z;
             else if (!cand_ids || col.id != aid[h][r]) nce_online(m[h][r], s[h][r], z);
           }
         }
@@ -361,8 +397,7 @@ __device__ __forceinline__ float nce_weight(double z, double l, float q, bool po
 // the partial da^ = W diag(invc) . C of a share; wave w owns the columns 16 ND w .. 16 ND (w + 1) - 1
 template <int ND>
 __global__ void __launch_bounds__(256)
-    nce_da_kernel(const float* __restrict__ a, const float* __restrict__ p, const float* __restrict__ n, int B, int D,
-                  float scale, const long long* __restrict__ cand_ids, const float* __restrict__ mem,
+    nce_da_kernel(const float* __restrict__ a, const float* __restrict__ r0, const float* __restrict__ r1, const float* __restrict__ mem, NceGeo geo, float scale, const long long* __restrict__ cand_ids,
                   const long long* __restrict__ mem_ids, const long long* __restrict__ mem_state, int M, int vec,
                   const double* __restrict__ inva, const double* __restrict__ invc, const double* __restrict__ invm,
                   const double* __restrict__ L, const float* __restrict__ q, float* __restrict__ part_da, int nta,
@@ -373,7 +408,8 @@ __global__ void __launch_bounds__(256)
   __shared__ __attribute__((aligned(16))) float Cs[NCE_TC * NCE_LD];
   __shared__ __attribute__((aligned(16))) float Wt[NCE_TA * NCE_WLD];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, g = lane >> 4;
-  NcePool pl{p, n, mem, B, D, 2 * B + nce_filled(mem, mem_state, M)};
+  const NcePool pl = nce_open(r0, r1, mem, geo, mem_state, M);
+  const int B = pl.B, D = pl.D;
   const int i0 = tile * NCE_TA;
   const int dbase = w * 16 * ND;
   double ia[2][4], li[2][4];
@@ -387,7 +423,7 @@ __global__ void __launch_bounds__(256)
       ia[h][r] = inva[i];
       li[h][r] = L[i];
       qi[h][r] = q[i];
-      aid[h][r] = cand_ids ? cand_ids[i] : 0;
+      aid[h][r] = cand_ids ? cand_ids[pl.pos0 + i] : 0;
     }
   f32x4 dacc[2][ND];
 #pragma unroll
@@ -406,7 +442,7 @@ __global__ void __launch_bounds__(256)
       for (int r = 0; r < 4; ++r) {
         const int i = i0 + 16 * h + 4 * g + r;
         const bool live = col.valid && i < B;
-        const bool pos = live && col.c == i;
+        const bool pos = live && col.rel == i;
         const bool neg = live && !pos && (!cand_ids || col.id != aid[h][r]);
         const double z = nce_z(acc[h][r], ia[h][r], col.inv, scale);
         const float wv = live ? nce_weight(z, li[h][r], qi[h][r], pos, neg) : 0.f;
@@ -443,23 +479,25 @@ __global__ void __launch_bounds__(256)
       }
 }
 
-// dc^ (before scale / B) of the candidates c0 .. c0 + 63 of [p; n], columns d0 .. d0 + 255:
+// dc^ (before scale / B) of the batch candidates c0 .. c0 + 63, columns d0 .. d0 + 255:
 // wave w owns the candidates 16 w .. 16 w + 15, walks every anchor tile
 __global__ void __launch_bounds__(256)
-    nce_dc_kernel(const float* __restrict__ a, const float* __restrict__ p, const float* __restrict__ n, int B, int D,
-                  float scale, const long long* __restrict__ cand_ids, int vec, const double* __restrict__ inva,
+    nce_dc_kernel(const float* __restrict__ a, const float* __restrict__ r0, const float* __restrict__ r1, NceGeo geo, float scale, const long long* __restrict__ cand_ids, int vec,
+                  const double* __restrict__ inva,
                   const double* __restrict__ invc, const double* __restrict__ L, const float* __restrict__ q,
                   float* __restrict__ dchat) {
   __shared__ __attribute__((aligned(16))) float As[NCE_TA * NCE_LD];
   __shared__ __attribute__((aligned(16))) float Cs[NCE_TC * NCE_LD];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, g = lane >> 4;
-  NcePool pl{p, n, nullptr, B, D, 2 * B};
+  const NcePool pl = nce_open(r0, r1, nullptr, geo, nullptr, 0);  // the batch candidates alone: no slot of the ring
+  const int B = pl.B, D = pl.D, nb = pl.nb;
   const int c0 = blockIdx.x * NCE_TC, d0 = blockIdx.y * NCE_DC_COLS;
-  NceCol col;  // of [p; n] alone: no slot of the ring
+  NceCol col;
   col.c = c0 + 16 * w + l15;
-  col.valid = col.c < 2 * B;
-  col.inv = invc[min(col.c, 2 * B - 1)];
-  col.id = cand_ids ? cand_ids[min(col.c, 2 * B - 1)] : 0;
+  col.rel = col.c - pl.pos0;
+  col.valid = col.c < nb;
+  col.inv = invc[min(col.c, nb - 1)];
+  col.id = cand_ids ? cand_ids[min(col.c, nb - 1)] : 0;
   constexpr int NT = NCE_DC_COLS / 16;
   f32x4 dacc[NT];
 #pragma unroll
@@ -473,8 +511,8 @@ __global__ void __launch_bounds__(256)
       for (int r = 0; r < 4; ++r) {
         const int i = i0 + 16 * h + 4 * g + r, ic = min(i, B - 1);
         const bool live = col.valid && i < B;
-        const bool pos = live && col.c == i;
-        const bool neg = live && !pos && (!cand_ids || col.id != cand_ids[ic]);
+        const bool pos = live && col.rel == i;
+        const bool neg = live && !pos && (!cand_ids || col.id != cand_ids[pl.pos0 + ic]);
         const double iav = inva[ic];
         const double z = nce_z(acc[h][r], iav, col.inv, scale);
         const float wv = live ? nce_weight(z, L[ic], q[ic], pos, neg) : 0.f;
@@ -496,25 +534,30 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int c = c0 + 16 * w + 4 * g + r, d = d0 + 16 * dt + l15;
-      if (c < 2 * B && d < D) dchat[(long long)c * D + d] = dacc[dt][r];
+      if (c < nb && d < D) dchat[(long long)c * D + d] = dacc[dt][r];
     }
 }
 
-// a wave per row of [da; dp; dn]: dx^ = scale / B * (the partials in share order | the
-// dc^ row), then the backward of x^ = x / max(|x|, eps)
+// a wave per row of da and of the batch candidates' gradient (d0 [split][D], then d1): dx^ =
+// scale / B * (the partials in share order | the dc^ row), then the backward of
+// x^ = x / max(|x|, eps)
 __global__ void __launch_bounds__(256)
-    nce_finish_kernel(const float* __restrict__ a, const float* __restrict__ p, const float* __restrict__ n, int B, int D,
-                      float scale, float eps, const float* __restrict__ part_da, int nshare,
-                      const float* __restrict__ dchat, float* __restrict__ da, float* __restrict__ dp,
-                      float* __restrict__ dn) {
+    nce_finish_kernel(const float* __restrict__ a, const float* __restrict__ r0, const float* __restrict__ r1, NceGeo geo, float scale, float eps,
+                      const float* __restrict__ part_da, int nshare, const float* __restrict__ dchat,
+                      float* __restrict__ da, float* __restrict__ d0, float* __restrict__ d1) {
   const int lane = threadIdx.x & 63;
   const long long r = blockIdx.x * 4LL + (threadIdx.x >> 6);
-  if (r >= 3LL * B) return;
+  const NcePool pl = nce_open(r0, r1, nullptr, geo, nullptr, 0);
+  const int B = pl.B, D = pl.D;
+  if (r >= (long long)B + pl.nb) return;
   const float* x;
   float* out;
   if (r < B) { x = a + r * D; out = da + r * D; }
-  else if (r < 2LL * B) { x = p + (r - B) * D; out = dp + (r - B) * D; }
-  else { x = n + (r - 2LL * B) * D; out = dn + (r - 2LL * B) * D; }
+  else {
+    const int c = (int)(r - B);
+    x = nce_row(pl, c);
+    out = c < pl.split ? d0 + (long long)c * D : d1 + (long long)(c - pl.split) * D;
+  }
   const float nrm = sqrtf(wave_sqnorm(x, D, lane));
   const float den = fmaxf(nrm, eps);  // divisions, not an inverse: at D = 1 x^ is +-1 and dx 0, exactly
   const float sb = scale / (float)B;
@@ -566,26 +609,26 @@ static NcePlan nce_plan(int B, int D) {
   return pn;
 }
 
-// f64 first (offsets in doubles): inva [B], invc [2B], invm [M], zpos [B], L [B],
+// f64 first (offsets in doubles): inva [B], invc [nb], invm [M], zpos [B], L [B],
 // part [ns_fwd][B][2] = (max, sum); then f32 (offsets in floats from the f64 part's end):
-// dchat [2B][D], part_da [ns_da][B][D]; bytes: the whole
+// dchat [nb][D], part_da [ns_da][B][D]; bytes: the whole.  nb: the batch candidates (2B | Nc)
 struct NceWs {
   long long inva, invc, invm, zpos, L, part, nd, dchat, part_da, bytes;
 };
 
-static NceWs nce_ws(int B, int D, int M, bool with_grad) {
+static NceWs nce_ws(int B, int nb, int D, int M, bool with_grad) {
   const NcePlan pn = nce_plan(B, D);
   NceWs o;
   long long at = 0;
   o.inva = at; at += B;
-  o.invc = at; at += 2LL * B;
+  o.invc = at; at += nb;
   o.invm = at; at += M;
   o.zpos = at; at += B;
   o.L = at; at += B;
   o.part = at; at += 2LL * pn.ns_fwd * B;
   o.nd = at;
   at = 0;
-  o.dchat = at; at += with_grad ? 2LL * B * D : 0;
+  o.dchat = at; at += with_grad ? (long long)nb * D : 0;
   o.part_da = at; at += with_grad ? (long long)pn.ns_da * B * D : 0;
   o.bytes = 8 * o.nd + 4 * at;
   return o;
@@ -599,13 +642,94 @@ static bool nce_shape_ok(const char* name, int B, int D, int M) {
   return true;
 }
 
+// the pool form's own: B <= Nc, and Nc + M far enough below 2^31 that a tile's last
+// column index (a multiple of the tile past the last candidate) still is an int
+#define NCE_MAX_POOL (2147483647LL - 4 * NCE_TC)
+static bool nce_pool_shape_ok(const char* name, int B, int Nc, int D, int M) {
+  if (!nce_shape_ok(name, B, D, M)) return false;
+  if (Nc < B) { set_error("%s: Nc=%d below B=%d", name, Nc, B); return false; }
+  if ((long long)Nc + M > NCE_MAX_POOL) {
+    set_error("%s: Nc=%d + M=%d above 2^31 - %d", name, Nc, M, 4 * NCE_TC + 1);
+    return false;
+  }
+  return true;
+}
+
+// what both entry points do once their own arguments are checked: the ring's pointers, the
+// workspace, then the launches.  pl: all but ctot; d0, d1: the candidates' gradient as
+// nce_finish_kernel takes it (all of da, d0, d1 NULL: forward alone)
+static int nce_run(const char* name, const float* a, NcePool pl, float scale, float eps, const long long* cand_ids,
+                   const long long* mem_ids, const long long* mem_state, int M, float* loss, float* rows, float* q,
+                   float* da, float* d0, float* d1, void* ws, long long ws_bytes, void* stream) {
+  const int B = pl.B, D = pl.D;
+  const bool ring = pl.mem != nullptr && M > 0;
+  if (ring && !mem_state) { set_error("%s: mem given with mem_state NULL", name); return -1; }
+  if (ring && cand_ids && !mem_ids) { set_error("%s: mem and cand_ids given with mem_ids NULL", name); return -1; }
+  const bool grad = da != nullptr;
+  const NceWs o = nce_ws(B, pl.nb, D, M, grad);
+  if (!ws || ws_bytes < o.bytes) {
+    set_error("%s: workspace of %lld bytes, %lld needed", name, ws ? ws_bytes : 0LL, o.bytes);
+    return -1;
+  }
+  if (((uintptr_t)ws & 7) != 0) { set_error("%s: workspace not 8-byte aligned", name); return -1; }
+  hipStream_t st = (hipStream_t)stream;
+  if (!ring) { pl.mem = nullptr; M = 0; }
+  const NceGeo geo{pl.B, pl.D, pl.split, pl.nb, pl.pos0};
+  double* dw = (double*)ws;
+  double *inva = dw + o.inva, *invc = dw + o.invc, *invm = dw + o.invm, *zpos = dw + o.zpos, *L = dw + o.L;
+  double* part = dw + o.part;
+  float* f = (float*)(dw + o.nd);
+  float *dchat = f + o.dchat, *part_da = f + o.part_da;
+  // 16-byte loads of the rows: every row start must be aligned
+  const uintptr_t al = (uintptr_t)a | (uintptr_t)pl.c0 | (uintptr_t)pl.c1 | (uintptr_t)pl.mem;
+  const int vec = (D % 4 == 0 && (al & 15) == 0) ? 1 : 0;
+  const NcePlan pn = nce_plan(B, D);
+  const int nct = (int)(((long long)pl.nb + M + NCE_TC - 1) / NCE_TC);  // tiles of the whole pool: the grid is sized from M
+  const int ns_fwd = pn.ns_fwd < nct ? pn.ns_fwd : nct;
+  const int ns_da = pn.ns_da < nct ? pn.ns_da : nct;
+
+  long long gp = ((long long)B + pl.nb + M + 3) / 4;
+  if (gp > 4096) gp = 4096;
+  hipLaunchKernelGGL(nce_prep_kernel, dim3((unsigned)gp), dim3(256), 0, st, a, pl.c0, pl.c1, pl.mem, geo, eps, mem_state, M, inva,
+                     invc, invm);
+  hipLaunchKernelGGL(nce_fwd_kernel, dim3((unsigned)(8 * ((pn.nta * ns_fwd + 7) / 8))), dim3(256), 0, st, a, pl.c0, pl.c1,
+                     pl.mem, geo, scale,
+                     cand_ids, mem_ids, mem_state, M, vec, inva, invc, invm, zpos, part, pn.nta, ns_fwd);
+  hipLaunchKernelGGL(nce_lse_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, part, ns_fwd, zpos, B, L, rows,
+                     q);
+  hipLaunchKernelGGL(nce_mean_kernel, dim3(1), dim3(256), 0, st, rows, B, loss);
+  if (grad) {
+    const dim3 gda((unsigned)(8 * ((pn.nta * ns_da + 7) / 8)));
+#define NCE_DA(ND)                                                                                                   \
+  hipLaunchKernelGGL(nce_da_kernel<ND>, gda, dim3(256), 0, st, a, pl.c0, pl.c1, pl.mem, geo, scale, cand_ids, mem_ids, mem_state, M, vec, inva, \
+                     invc, invm, L, q, part_da, pn.nta, ns_da)
+    if (D <= 256) NCE_DA(4);
+    else if (D <= 512) NCE_DA(8);
+    else NCE_DA(16);
+#undef NCE_DA
+    const dim3 gdc((unsigned)((pl.nb + NCE_TC - 1) / NCE_TC), (unsigned)((D + NCE_DC_COLS - 1) / NCE_DC_COLS));
+    hipLaunchKernelGGL(nce_dc_kernel, gdc, dim3(256), 0, st, a, pl.c0, pl.c1, geo, scale, cand_ids, vec, inva, invc, L, q,
+                       dchat);
+    hipLaunchKernelGGL(nce_finish_kernel, dim3((unsigned)(((long long)B + pl.nb + 3) / 4)), dim3(256), 0, st, a, pl.c0,
+                       pl.c1, geo, scale, eps, part_da, ns_da, dchat, da, d0, d1);
+  }
+  ARTSBIR_CHECK_LAUNCH(name);
+  return 0;
+}
+
+static bool nce_scale_ok(const char* name, float scale) {
+  if (scale > 0.f && std::isfinite(scale)) return true;
+  set_error("%s: scale=%g must be finite and > 0", name, (double)scale);
+  return false;
+}
+
 }  // namespace artsbir
 
 using namespace artsbir;
 
 extern "C" long long artsbir_info_nce_workspace(int B, int D, int M, int with_grad) {
   if (!nce_shape_ok("info_nce_workspace", B, D, M)) return -1;
-  return nce_ws(B, D, M, with_grad != 0).bytes;
+  return nce_ws(B, 2 * B, D, M, with_grad != 0).bytes;
 }
 
 extern "C" int artsbir_info_nce(const float* a, const float* p, const float* n, int B, int D, float scale, float eps,
@@ -613,59 +737,34 @@ extern "C" int artsbir_info_nce(const float* a, const float* p, const float* n, 
                                 const long long* mem_state, int M, float* loss, float* rows, float* q, float* da,
                                 float* dp, float* dn, void* ws, long long ws_bytes, void* stream) {
   if (!nce_shape_ok("info_nce", B, D, M)) return -1;
-  if (!(scale > 0.f) || !std::isfinite(scale)) { set_error("info_nce: scale=%g must be finite and > 0", (double)scale); return -1; }
+  if (!nce_scale_ok("info_nce", scale)) return -1;
   if (!a || !p || !n || !loss || !rows || !q) { set_error("info_nce: NULL pointer"); return -1; }
   const int ngrad = (da != nullptr) + (dp != nullptr) + (dn != nullptr);
   if (ngrad != 0 && ngrad != 3) { set_error("info_nce: da, dp, dn must be given together or not at all"); return -1; }
-  const bool ring = mem != nullptr && M > 0;
-  if (ring && !mem_state) { set_error("info_nce: mem given with mem_state NULL"); return -1; }
-  if (ring && cand_ids && !mem_ids) { set_error("info_nce: mem and cand_ids given with mem_ids NULL"); return -1; }
-  const bool grad = ngrad == 3;
-  const NceWs o = nce_ws(B, D, M, grad);
-  if (!ws || ws_bytes < o.bytes) {
-    set_error("info_nce: workspace of %lld bytes, %lld needed", ws ? ws_bytes : 0LL, o.bytes);
+  const NcePool pl{p, n, mem, B, D, B, 2 * B, 0, 0};
+  return nce_run("info_nce", a, pl, scale, eps, cand_ids, mem_ids, mem_state, M, loss, rows, q, da, dp, dn, ws, ws_bytes,
+                 stream);
+}
+
+extern "C" long long artsbir_info_nce_pool_workspace(int B, int Nc, int D, int M, int with_grad) {
+  if (!nce_pool_shape_ok("info_nce_pool_workspace", B, Nc, D, M)) return -1;
+  return nce_ws(B, Nc, D, M, with_grad != 0).bytes;
+}
+
+extern "C" int artsbir_info_nce_pool(const float* a, const float* cand, int B, int Nc, int pos0, int D, float scale,
+                                     float eps, const long long* cand_ids, const float* mem, const long long* mem_ids,
+                                     const long long* mem_state, int M, float* loss, float* rows, float* q, float* da,
+                                     float* dcand, void* ws, long long ws_bytes, void* stream) {
+  if (!nce_pool_shape_ok("info_nce_pool", B, Nc, D, M)) return -1;
+  if (pos0 < 0) { set_error("info_nce_pool: pos0=%d must be >= 0", pos0); return -1; }
+  if ((long long)pos0 + B > Nc) { set_error("info_nce_pool: pos0=%d + B=%d above Nc=%d", pos0, B, Nc); return -1; }
+  if (!nce_scale_ok("info_nce_pool", scale)) return -1;
+  if (!a || !cand || !loss || !rows || !q) { set_error("info_nce_pool: NULL pointer"); return -1; }
+  if ((da != nullptr) != (dcand != nullptr)) {
+    set_error("info_nce_pool: da and dcand must be given together or not at all");
     return -1;
   }
-  if (((uintptr_t)ws & 7) != 0) { set_error("info_nce: workspace not 8-byte aligned"); return -1; }
-  hipStream_t st = (hipStream_t)stream;
-  if (!ring) { mem = nullptr; M = 0; }
-  double* dw = (double*)ws;
-  double *inva = dw + o.inva, *invc = dw + o.invc, *invm = dw + o.invm, *zpos = dw + o.zpos, *L = dw + o.L;
-  double* part = dw + o.part;
-  float* f = (float*)(dw + o.nd);
-  float *dchat = f + o.dchat, *part_da = f + o.part_da;
-  // 16-byte loads of the rows: every row start must be aligned
-  const uintptr_t al = (uintptr_t)a | (uintptr_t)p | (uintptr_t)n | (uintptr_t)mem;
-  const int vec = (D % 4 == 0 && (al & 15) == 0) ? 1 : 0;
-  const NcePlan pn = nce_plan(B, D);
-  const int nct = (int)((2LL * B + M + NCE_TC - 1) / NCE_TC);  // tiles of the whole pool: the grid is sized from M
-  const int ns_fwd = pn.ns_fwd < nct ? pn.ns_fwd : nct;
-  const int ns_da = pn.ns_da < nct ? pn.ns_da : nct;
-
-  long long gp = (3LL * B + M + 3) / 4;
-  if (gp > 4096) gp = 4096;
-  hipLaunchKernelGGL(nce_prep_kernel, dim3((unsigned)gp), dim3(256), 0, st, a, p, n, B, D, eps, mem, mem_state, M, inva,
-                     invc, invm);
-  hipLaunchKernelGGL(nce_fwd_kernel, dim3((unsigned)(8 * ((pn.nta * ns_fwd + 7) / 8))), dim3(256), 0, st, a, p, n, B, D,
-                     scale, cand_ids, mem, mem_ids, mem_state, M, vec, inva, invc, invm, zpos, part, pn.nta, ns_fwd);
-  hipLaunchKernelGGL(nce_lse_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, part, ns_fwd, zpos, B, L, rows,
-                     q);
-  hipLaunchKernelGGL(nce_mean_kernel, dim3(1), dim3(256), 0, st, rows, B, loss);
-  if (grad) {
-    const dim3 gda((unsigned)(8 * ((pn.nta * ns_da + 7) / 8)));
-#define NCE_DA(ND)                                                                                                  \
-  hipLaunchKernelGGL(nce_da_kernel<ND>, gda, dim3(256), 0, st, a, p, n, B, D, scale, cand_ids, mem, mem_ids, mem_state, \
-                     M, vec, inva, invc, invm, L, q, part_da, pn.nta, ns_da)
-    if (D <= 256) NCE_DA(4);
-    else if (D <= 512) NCE_DA(8);
-    else NCE_DA(16);
-#undef NCE_DA
-    const dim3 gdc((unsigned)((2 * B + NCE_TC - 1) / NCE_TC), (unsigned)((D + NCE_DC_COLS - 1) / NCE_DC_COLS));
-    hipLaunchKernelGGL(nce_dc_kernel, gdc, dim3(256), 0, st, a, p, n, B, D, scale, cand_ids, vec, inva, invc, L, q,
-                       dchat);
-    hipLaunchKernelGGL(nce_finish_kernel, dim3((unsigned)((3LL * B + 3) / 4)), dim3(256), 0, st, a, p, n, B, D, scale,
-                       eps, part_da, ns_da, dchat, da, dp, dn);
-  }
-  ARTSBIR_CHECK_LAUNCH("info_nce");
-  return 0;
+  const NcePool pl{cand, cand, mem, B, D, Nc, Nc, pos0, 0};
+  return nce_run("info_nce_pool", a, pl, scale, eps, cand_ids, mem_ids, mem_state, M, loss, rows, q, da, dcand, dcand, ws,
+                 ws_bytes, stream);
 }

@@ -13,7 +13,8 @@
   CrossBatchMemory             a ring of past gallery-side embeddings on the device that the
                                mining above can search as well (an addition)
   info_nce / InfoNCELoss       the softmax contrastive loss over all 2B gallery-side rows of
-                               the step and that ring (an addition)
+                               the step and that ring (an addition); gather=True: over the rows
+                               of every rank, their gradients sent home in the backward
 All run on the GPU kernels with explicit backward kernels.
 """
 from __future__ import annotations
@@ -281,9 +282,11 @@ class CrossBatchMemory:
                              f"{tuple(rows.shape)} on {rows.device}")
 
     @torch.no_grad()
-    def enqueue(self, rows, ids=None):
+    def enqueue(self, rows, ids=None, gathered=False):
         """rows [R, dim] (ids int64 [R] or None) into the ring, row r at slot (head + r) mod
-        size; with more than one rank every rank's rows first, rank-major"""
+        size; with more than one rank every rank's rows first, rank-major.  gathered=True:
+        rows and ids are every rank's already, rank-major and the same on all ranks (the
+        gather of a step that has done it), and are not gathered again"""
         _cuda(rows)
         rows = rows.detach().contiguous().float()
         self._ready(rows)
@@ -292,7 +295,8 @@ class CrossBatchMemory:
             ids = ids.detach().contiguous().to(torch.int64)
             if ids.shape != (rows.shape[0],):
                 raise ValueError(f"ids must have shape [{rows.shape[0]}], not {tuple(ids.shape)}")
-        rows, ids = _gather_ranks(rows, ids)
+        if not gathered:
+            rows, ids = _gather_ranks(rows, ids)
         call("artsbir_xbm_enqueue", ptr(rows), ptr(ids), rows.shape[0], self.dim, ptr(self.mem), ptr(self.mem_ids),
              ptr(self.mem_state), self.size, _s())
 
@@ -498,45 +502,186 @@ class _InfoNCEFn(torch.autograd.Function):
                 None, None, None, None)
 
 
-def info_nce(a, p, n, temperature=0.07, cand_ids=None, memory=None, eps=1e-8):
+def _info_nce_pool_raw(a, cand, pos0, temperature, cand_ids, memory, eps, with_grad):
+    """one artsbir_info_nce_pool call: anchors a [B, D] against the candidates cand [Nc, D]
+    (ids cand_ids [Nc] or None) and the memory's filled slots, anchor i's positive at
+    cand[pos0 + i] -> (loss [], rows [B], q [B], (da [B, D], dcand [Nc, D]) or None)"""
+    _cuda(a, cand)
+    a, cand = (t.detach().contiguous().float() for t in (a, cand))
+    if not (a.dim() == 2 and cand.dim() == 2 and a.shape[1] == cand.shape[1]):
+        raise ValueError(f"a [B, D] and cand [Nc, D] must share D: {tuple(a.shape)} {tuple(cand.shape)}")
+    temperature = float(temperature)
+    if not temperature > 0:
+        raise ValueError(f"temperature must be > 0, not {temperature}")
+    (B, D), Nc = a.shape, cand.shape[0]
+    if cand_ids is not None:
+        _cuda(cand_ids)
+        cand_ids = cand_ids.detach().contiguous().to(torch.int64)
+        if cand_ids.shape != (Nc,):
+            raise ValueError(f"cand_ids must have shape [{Nc}], not {tuple(cand_ids.shape)}")
+    mem = mem_ids = mem_state = None
+    M = 0
+    if memory is not None:
+        memory._ready(a)
+        mem, mem_ids, mem_state, M = memory.mem, memory.mem_ids, memory.mem_state, memory.size
+    nbytes = _hip.lib().artsbir_info_nce_pool_workspace(B, Nc, D, M, int(with_grad))
+    if nbytes < 0:
+        raise _hip.HipError(_hip.lib().artsbir_last_error().decode(errors="replace"))
+    ws = torch.empty(max(int(nbytes), 4), dtype=torch.uint8, device=a.device)
+    loss = torch.empty((), dtype=torch.float32, device=a.device)
+    rows, q = (torch.empty(B, dtype=torch.float32, device=a.device) for _ in range(2))
+    grads = (torch.empty_like(a), torch.empty_like(cand)) if with_grad else (None, None)
+    call("artsbir_info_nce_pool", ptr(a), ptr(cand), B, Nc, int(pos0), D, 1.0 / temperature, float(eps), ptr(cand_ids),
+         ptr(mem), ptr(mem_ids), ptr(mem_state), M, ptr(loss), ptr(rows), ptr(q), ptr(grads[0]), ptr(grads[1]), ptr(ws),
+         int(nbytes), _s())
+    return loss, rows, q, (grads if with_grad else None)
+
+
+def _reduce_rows(rows):
+    """the sum of rows [world * R, D] over the ranks; this rank keeps its own R rows:
+    reduce_scatter_tensor where the backend has it, all_reduce and a slice on gloo (chosen
+    as ddp._avg_op chooses)"""
+    import torch.distributed as dist
+    world, rank = dist.get_world_size(), dist.get_rank()
+    R = rows.shape[0] // world
+    rows = rows.contiguous()
+    if dist.get_backend() == "nccl":
+        own = rows.new_empty((R,) + tuple(rows.shape[1:]))
+        dist.reduce_scatter_tensor(own, rows, op=dist.ReduceOp.SUM)
+        return own
+    dist.all_reduce(rows, op=dist.ReduceOp.SUM)
+    return rows[rank * R:(rank + 1) * R]
+
+
+def _gathering() -> bool:
+    """gather=True takes effect: gradients enabled and a process group of more than one rank"""
+    import torch.distributed as dist
+    return (torch.is_grad_enabled() and dist.is_available() and dist.is_initialized()
+            and dist.get_world_size() > 1)
+
+
+class _InfoNCEGatherFn(torch.autograd.Function):
+    """The loss of this rank's anchors against G = every rank's [p; n], rank-major (this
+    rank's own rows start at pos0 = rank * 2B), and the ring.  The forward takes da and
+    dG from the kernel (the ring changes right after it); the backward scales them by
+    gout, which is rank-local, sums gout * dG over the ranks and keeps this rank's rows:
+    the gradient of sum_s loss_s with respect to its own p and n."""
+
+    @staticmethod
+    def forward(ctx, a, p, n, G, ids_G, pos0, temperature, memory, eps, kernel, reduce_rows):
+        with_grad = any(ctx.needs_input_grad[:3])
+        loss, rows, q, grads = kernel(a.detach(), G, pos0, temperature, ids_G, memory, eps, with_grad)
+        if with_grad:
+            ctx.save_for_backward(*grads)
+        ctx.reduce_rows = reduce_rows
+        ctx.mark_non_differentiable(q)
+        return loss, q
+
+    @staticmethod
+    def backward(ctx, gout, _gq):
+        da, dG = ctx.saved_tensors
+        B = da.shape[0]
+        own = ctx.reduce_rows(gout * dG)  # a collective: every rank runs this backward
+        need = ctx.needs_input_grad
+        return (gout * da if need[0] else None, own[:B] if need[1] else None, own[B:] if need[2] else None,
+                None, None, None, None, None, None, None, None)
+
+
+def _info_nce(a, p, n, temperature, cand_ids, memory, eps, gather, kernel, all_gather, reduce_rows):
+    """(loss, q, gathered): gathered = (G, ids_G) of the step when the gather took effect,
+    None when the local call ran"""
+    if not (gather and _gathering()):
+        if kernel is None:
+            loss, q = _InfoNCEFn.apply(a, p, n, temperature, cand_ids, memory, eps)
+        else:  # a stand-in for the kernel: the local call in the pool form
+            loss, q = _InfoNCEGatherFn.apply(a, p, n, torch.cat((p, n)).detach(), cand_ids, 0, temperature, memory,
+                                             eps, kernel, lambda rows: rows)
+        return loss, q, None
+    import torch.distributed as dist
+    if not (a.dim() == 2 and a.shape == p.shape == n.shape):
+        raise ValueError(f"a, p, n must share one [B, D] shape: {tuple(a.shape)} {tuple(p.shape)} {tuple(n.shape)}")
+    if cand_ids is not None:
+        cand_ids = cand_ids.detach().contiguous().to(torch.int64)
+        if cand_ids.shape != (2 * a.shape[0],):
+            raise ValueError(f"cand_ids must have shape [{2 * a.shape[0]}], not {tuple(cand_ids.shape)}")
+    G, ids_G = (all_gather or _gather_ranks)(torch.cat((p, n)).detach().float(), cand_ids)
+    loss, q = _InfoNCEGatherFn.apply(a, p, n, G, ids_G, dist.get_rank() * 2 * a.shape[0], temperature, memory, eps,
+                                     kernel or _info_nce_pool_raw, reduce_rows or _reduce_rows)
+    return loss, q, (G, ids_G)
+
+
+def info_nce(a, p, n, temperature=0.07, cand_ids=None, memory=None, eps=1e-8, gather=False, *, kernel=None,
+             all_gather=None, reduce_rows=None):
     """InfoNCE (softmax contrastive) loss of every anchor a[i] against its positive p[i] and
     every other gallery-side row of the step, C = [p; n], and of a CrossBatchMemory's filled
     slots: mean over i of -log softmax_i(positive) of the logits cos(a[i], c) / temperature.
     Candidate c != i is a negative unless cand_ids (int64 [2B], the photo of every row of C)
     is given and the candidate's photo (cand_ids[c], memory.mem_ids[j]) is cand_ids[i].
     Exact f32 on the f32-input MFMA; the logit matrix never exists in memory; two runs give
-    the same bytes.  Gradients flow to a, p and n; ring rows are constants."""
-    return _InfoNCEFn.apply(a, p, n, temperature, cand_ids, memory, eps)[0]
+    the same bytes.  Gradients flow to a, p and n; ring rows are constants.
+
+    gather=True, with gradients enabled under an initialised process group of more than one
+    rank (otherwise the call above runs unchanged: no group, one rank, torch.no_grad()): the
+    candidates are the rows of EVERY rank, G = all_gather(cat(p, n).detach()) rank-major with
+    cand_ids gathered alike, in one artsbir_info_nce_pool call (Nc = 2B world, the positives
+    at rank 2B + i); every rank passes the same B.  The value is the mean over this rank's
+    anchors.  The backward returns gout da, and sums gout dG over the ranks and keeps the
+    rows of this rank's own p and n (reduce_scatter_tensor; all_reduce and a slice on gloo):
+    rank r back-propagates d(sum_s loss_s) / d(its own rows), so the parameter gradient that
+    ddp averages over the ranks is that of the mean loss over all world B anchors.  That sum
+    is a collective in the backward (gout is rank-local): every rank must run the backward of
+    every gathered loss, as for any data-parallel step.  It is issued from the host before
+    the encoder's backward starts, so it precedes the reducer's bucket all-reduces on every
+    rank alike.  The ranks must also agree on whether any of a, p, n requires a gradient:
+    a rank whose inputs need none takes no gradients in the forward and never enters that
+    collective, and the others would wait for it.
+    kernel / all_gather / reduce_rows (keyword only) stand in for the kernel call
+    (_info_nce_pool_raw's signature) and the two collectives (_gather_ranks, _reduce_rows),
+    as knn.knn_sharded's local_search / merge do: tests run the protocol without a GPU.
+    A kernel stand-in replaces the local call too (where the gather does not take effect
+    it is called in the pool form, cand = [p; n] and pos0 = 0, in place of
+    artsbir_info_nce), so a test that passes one never reaches the device."""
+    return _info_nce(a, p, n, temperature, cand_ids, memory, eps, gather, kernel, all_gather, reduce_rows)[0]
 
 
 class InfoNCELoss(nn.Module):
-    """forward(a, p, n, cand_ids=None) = info_nce(a, p, n, temperature, cand_ids, memory).
+    """forward(a, p, n, cand_ids=None) = info_nce(a, p, n, temperature, cand_ids, memory,
+    gather=gather).
     memory (a CrossBatchMemory, default None): with gradients enabled the ring's filled slots
     are negatives too, and cat(p, n).detach() with cand_ids is enqueued after the loss has
     read the ring, so a step never meets its own rows; under torch.no_grad() the ring is
     neither read nor written.  A device counter (no host synchronisation) follows the
     probability of the positive, 1 - q, over the anchors seen with gradients enabled;
-    positive_probability() reads and resets it."""
+    positive_probability() reads and resets it.
+    gather=True (see info_nce; it takes effect with gradients enabled under more than one
+    rank): every rank's rows are candidates, their gradients go home in the backward, which
+    every rank must run; the gathered rows are what the ring receives, so a gathered step
+    does one all-gather, not two.  kernel / all_gather / reduce_rows: info_nce's stand-ins."""
 
     margin = None  # there is no margin: the triplet losses' attribute, for the training record
 
-    def __init__(self, temperature: float = 0.07, memory=None):
+    def __init__(self, temperature: float = 0.07, memory=None, gather=False, *, kernel=None, all_gather=None,
+                 reduce_rows=None):
         super().__init__()
         if not float(temperature) > 0:
             raise ValueError(f"temperature must be > 0, not {temperature}")
-        self.temperature, self.memory = float(temperature), memory
+        self.temperature, self.memory, self.gather = float(temperature), memory, bool(gather)
+        self._hooks = (kernel, all_gather, reduce_rows)
         self._sums = None  # f64 [2] on the device: anchors seen, sum of 1 - q
 
     def forward(self, anchor, positive, negative, cand_ids=None):
         grad = torch.is_grad_enabled()
         memory = self.memory if grad else None
-        loss, q = _InfoNCEFn.apply(anchor, positive, negative, self.temperature, cand_ids, memory, 1e-8)
+        loss, q, gathered = _info_nce(anchor, positive, negative, self.temperature, cand_ids, memory, 1e-8,
+                                      self.gather, *self._hooks)
         if grad:
             if self._sums is None or self._sums.device != q.device:
                 self._sums = torch.zeros(2, dtype=torch.float64, device=q.device)
             self._sums[0] += q.shape[0]
             self._sums[1] += (1.0 - q.double()).sum()
-            if memory is not None:
+            if memory is not None and gathered is not None:
+                memory.enqueue(*gathered, gathered=True)
+            elif memory is not None:
                 memory.enqueue(torch.cat((positive, negative)).detach(), cand_ids)
         return loss
 

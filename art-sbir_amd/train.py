@@ -25,7 +25,10 @@ Differences, all opt-in or documented:
     torch.distributed.run the ring holds every rank's rows, so negatives cross ranks;
   * ``--negatives all --loss_type cosine`` trains with the InfoNCE (softmax contrastive)
     loss over all 2 x batch gallery-side embeddings of the step and the ring
-    (losses.InfoNCELoss), at ``--temperature``.
+    (losses.InfoNCELoss), at ``--temperature``;
+  * ``--gather_negatives`` (with ``--negatives all``, under torch.distributed.run) makes the
+    gallery-side embeddings of every rank the candidates of that loss: one all-gather in the
+    forward, the gathered rows' gradients summed and sent home in the backward.
 """
 from __future__ import annotations
 
@@ -168,17 +171,20 @@ def _evaluate(model, loss_fn, loader, stale, limit):
 
 
 def make_loss(loss_type, with_classification, dataset_name, margin, negatives='given', memory_size=0,
-              temperature=None):
+              temperature=None, gather_negatives=False):
     """the reference's loss for the configuration; negatives 'hardest' / 'semihard' wraps
     it in losses.MinedNegatives with the metric of loss_type, 'all' gives losses.InfoNCELoss
     at `temperature` (default 0.07) instead; memory_size > 0 gives either a
     losses.CrossBatchMemory of memory_size rows (of the embeddings' width, allocated at the
-    first step)"""
+    first step); gather_negatives (with 'all') makes every rank's rows of the step the
+    loss's candidates (losses.InfoNCELoss(gather=True); no effect at one rank)"""
     _check_memory_size(memory_size, negatives)
     _check_contrastive(negatives, temperature, loss_type, with_classification)
+    _check_gather(gather_negatives, negatives)
     memory = losses.CrossBatchMemory(memory_size, None) if memory_size else None
     if negatives == 'all':
-        return losses.InfoNCELoss(DEFAULT_TEMPERATURE if temperature is None else temperature, memory=memory)
+        return losses.InfoNCELoss(DEFAULT_TEMPERATURE if temperature is None else temperature, memory=memory,
+                                  gather=bool(gather_negatives))
     loss_fn = _make_loss(loss_type, with_classification, dataset_name, margin)
     if negatives == 'given':
         return loss_fn
@@ -191,6 +197,12 @@ def _check_memory_size(memory_size, negatives):
     if memory_size and negatives == 'given':
         raise SystemExit("--memory_size needs --negatives hardest or semihard: the memory only adds candidates "
                          "to the mining")
+
+
+def _check_gather(gather_negatives, negatives):
+    if gather_negatives and negatives != 'all':
+        raise SystemExit("--gather_negatives needs --negatives all: only the InfoNCE loss takes the rows of every "
+                         "rank as candidates (the mined triplet losses stay in their shard)")
 
 
 DEFAULT_TEMPERATURE = 0.07
@@ -280,14 +292,20 @@ def parse_args(argv=None):
                         "the 2 x batch gallery-side embeddings of the step (losses.MinedNegatives; per process "
                         "under torch.distributed.run: the step's candidates are not exchanged between ranks, "
                         "--memory_size adds past rows of every rank); all: every one of them, by the InfoNCE "
-                        "loss (losses.InfoNCELoss; needs --loss_type cosine and no classification heads)")
+                        "loss (losses.InfoNCELoss; needs --loss_type cosine and no classification heads; "
+                        "--gather_negatives adds the step's rows of every other rank)")
     p.add_argument('--temperature', type=float, default=None,
                    help="temperature of the InfoNCE loss (--negatives all; default 0.07)")
     p.add_argument('--memory_size', type=int, default=0,
                    help="cross-batch memory: also mine among the last M gallery-side embeddings of earlier steps, "
                         "of every rank under torch.distributed.run (losses.CrossBatchMemory; 0 = off; needs "
                         "--negatives hardest or semihard)")
+    p.add_argument('--gather_negatives', action='store_true',
+                   help="--negatives all under torch.distributed.run: the candidates of the InfoNCE loss are the "
+                        "gallery-side embeddings of every rank, gathered in the forward, their gradients summed and "
+                        "returned to their rank in the backward (no effect in one process)")
     args = p.parse_args(argv)
+    _check_gather(args.gather_negatives, args.negatives)
     _check_memory_size(args.memory_size, args.negatives)
     _check_contrastive(args.negatives, args.temperature, args.loss_type, 'with_classification' in args.model_type)
     if args.negatives == 'all' and args.temperature is None:
@@ -332,7 +350,7 @@ def main(argv=None):
     optimizer = optim.Adam(model.parameters(), lr=args.learning_rate, weight_decay=args.weight_decay)
     with_classification = 'with_classification' in type(model).__name__ and 'V2' in train_dataset.state_dict['dataset']
     loss_fn = make_loss(args.loss_type, with_classification, train_dataset.state_dict['dataset'], utils.MARGIN,
-                        args.negatives, args.memory_size, args.temperature)
+                        args.negatives, args.memory_size, args.temperature, gather_negatives=args.gather_negatives)
     param_dict = {"model": args.model, "trained_layers": model.trained_layers, "dataset": args.dataset,
                   "epochs": args.epochs, "batch_size": args.batch_size, "learning_rate": args.learning_rate,
                   "weight_decay": args.weight_decay, "optimizer": type(optimizer).__name__,
@@ -344,6 +362,8 @@ def main(argv=None):
         param_dict["temperature"] = args.temperature
     if args.memory_size:
         param_dict["memory_size"] = args.memory_size
+    if args.gather_negatives:
+        param_dict["gather_negatives"] = True
     data_dict = train_dataset.state_dict
     print(param_dict, flush=True)
     print(data_dict, flush=True)

@@ -514,6 +514,25 @@ int artsbir_info_nce(const float* a, const float* p, const float* n, int B, int 
                      const long long* cand_ids, const float* mem, const long long* mem_ids,
                      const long long* mem_state, int M, float* loss, float* rows, float* q, float* da, float* dp,
                      float* dn, void* ws, long long ws_bytes, void* stream);
+/* The pool form of artsbir_info_nce, on the same kernels: the gradient-carrying candidates
+ * are one contiguous block cand [Nc][D] (every rank's gallery-side rows, say) of which the
+ * local anchors' positives are a slice.  Candidate c < Nc is cand[c], c = Nc + j is slot j
+ * of the ring for j < min(count, M); anchor i's positive is c = pos0 + i (0 <= pos0,
+ * pos0 + B <= Nc); every other candidate is a negative unless cand_ids (int64 [Nc]) is given
+ * and the candidate's id (cand_ids[c], mem_ids[j]) equals the anchor's, cand_ids[pos0 + i].
+ * Formulas, the stable form, exactness and NaN propagation are artsbir_info_nce's.  loss is
+ * the mean over the B anchors; da [B][D] and dcand [Nc][D] (both or neither) are its
+ * gradients for d loss = 1; every row of dcand is written, a row no anchor weighs as exact
+ * zeros.  With cand = [p; n] in one allocation, Nc = 2B and pos0 = 0, loss, rows, q and da
+ * are the bytes of artsbir_info_nce and dcand those of [dp; dn].  ws:
+ * artsbir_info_nce_pool_workspace bytes, 8-byte aligned.  1 <= B <= 2^20, B <= Nc,
+ * Nc + M <= 2^31 - 257, 1 <= D <= 1024, 0 <= M <= 2^24, scale finite and > 0; mem needs
+ * mem_state, and mem_ids when cand_ids is given.  Every refusal comes ahead of any launch. */
+long long artsbir_info_nce_pool_workspace(int B, int Nc, int D, int M, int with_grad);
+int artsbir_info_nce_pool(const float* a, const float* cand, int B, int Nc, int pos0, int D, float scale, float eps,
+                          const long long* cand_ids, const float* mem, const long long* mem_ids,
+                          const long long* mem_state, int M, float* loss, float* rows, float* q, float* da,
+                          float* dcand, void* ws, long long ws_bytes, void* stream);
 /* Adam over a device table of {param, grad, exp_avg, exp_avg_sq, numel} records
  * (host helpers size and fill the per-block table). */
 long long artsbir_adam_table_blocks(const long long* numels, int ntensors, long long chunk);
